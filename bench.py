@@ -28,6 +28,11 @@ The K timed steps are launched as ONE HIP graph in a short single-GPU run (`--la
 the timed region, launched once inside it) and one C-ABI call after the other otherwise; `config.launch` says which,
 `eager_ms_per_step` is the eager loop of the same K steps timed right behind the graph.
 
+`--dump-outputs DIR` writes what the last timed step computed -- the (B, N) score matrix a caller of the path receives,
+padding columns dropped -- as DIR/scores.npy (float32), taken right behind the timed region.  Above DUMP_BYTES it is a
+fixed, seeded sample of its rows, whose batch indices are DIR/scores_rows.npy (float64).  The operands and query batches
+are seeded, so two runs with the same arguments see the same inputs and their files can be compared one to one.
+
 Prints ONE JSON line on rank 0 (contract in the task description), with `roofline`
 for the dominant kernel (the score kernel: `kernel_ms` = its own begin -> end on HIP events
 handed to the launch, rtk_timer_* of the C ABI, on steps right behind the timed region;
@@ -64,6 +69,7 @@ WORKLOADS = {
 }
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 EVAL_BATCHES = 16      # --tables cached: the relation tables are rebuilt every this many steps (one "evaluation pass")
+DUMP_BYTES = 48 << 20  # --dump-outputs: at most this many bytes of scores (larger matrices: a seeded sample of rows)
 
 
 def score_kernel_name(n_loc, c):
@@ -231,8 +237,13 @@ def main():
                     help="multi-GPU: run the all-gather of step i before step i+1 starts (default: it overlaps the next step's kernels)")
     ap.add_argument("--force-dist", action="store_true",
                     help="rehearsal: run the multi-GPU code path (process group, collectives) with however many ranks there are, even one")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the scores of the last timed step to DIR/scores.npy (float32; a seeded sample of rows when "
+                         "the matrix exceeds %d MB, their batch indices in DIR/scores_rows.npy)" % (DUMP_BYTES >> 20))
     ap.add_argument("--launcher-selftest", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(launch_children(sys.argv[1:], args.gpus))
@@ -425,6 +436,19 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
+    # --dump-outputs: rows of the score matrix to keep (all of them when the matrix fits in DUMP_BYTES)
+    n_dump = min(B, max(1, DUMP_BYTES // (4 * n_ent)))
+    dump_rows = (np.arange(B) if n_dump == B else np.sort(np.random.default_rng(0).choice(B, n_dump, replace=False)))
+    dumped = None
+
+    def snapshot():
+        """The (B, N) scores of the last timed step as a caller receives them (the gather buffer holds each rank's
+        (B, n_loc) block in slot p; shards are contiguous row blocks of O, the last one zero-padded) -> host fp32."""
+        g = gathered_all[(args.warmup + args.steps - 1) % n_buf]
+        rows = torch.from_numpy(dump_rows).to(dev)
+        blk = g.index_select(1, rows)[:, :, :n_loc].float()               # (world, rows, n_loc)
+        return blk.permute(1, 0, 2).reshape(len(dump_rows), world * n_loc)[:, :n_ent].cpu().numpy()
+
     if args.prewarm_ms > 0:     # untimed: bring clocks, TLBs and the code objects to their steady state
         t_end = time.perf_counter() + args.prewarm_ms * 1e-3
         i = 0
@@ -477,6 +501,8 @@ def main():
         graph.replay()
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dumped = snapshot()
         barrier()
         t0 = time.perf_counter()
         for i in range(args.steps):
@@ -490,6 +516,8 @@ def main():
             step(args.warmup + i, events[i])
         barrier()
         dt = time.perf_counter() - t0
+        if args.dump_outputs and rank == 0:
+            dumped = snapshot()
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -717,6 +745,11 @@ def main():
             result["ranked_without_gather"] = {"error": repr(e)}
     if rank == 0 and world == 1 and not args.no_cpu_baseline and not bf16 and not args.force_dist:
         result["cpu_baseline"] = cpu_baseline(gen, n_ent, n_rel, B, trank, pool_cpu)
+    if dumped is not None:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "scores.npy"), np.ascontiguousarray(dumped, dtype=np.float32))
+        if n_dump < B:
+            np.save(os.path.join(args.dump_outputs, "scores_rows.npy"), dump_rows.astype(np.float64))
     if rank == 0:
         print(json.dumps(result), flush=True)
     if use_dist:

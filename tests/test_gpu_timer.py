@@ -64,3 +64,37 @@ def test_bench_line_in_both_launch_modes():
         assert 0 < r["kernel_ms"] <= r["stream_bracket_ms"] * 1.05 and r["kernel_ms_source"].startswith("kernel begin/end")
         assert abs(d["value"] - 12 * 512 / (d["ms_per_step"] * 12e-3)) < 1e-6 * d["value"]
     assert g["ms_per_step"] < 1.5 * e["ms_per_step"] and e["ms_per_step"] < 1.5 * g["ms_per_step"]
+
+
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """python bench.py --dump-outputs DIR: the scores of the last timed step (a seeded sample of rows of the WN18RR
+    matrix, which is over the size limit) match the oracle on the same seeded operands and batch; --steps is the
+    number of timed steps of the line."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    from oracle import score_oracle as orc
+    from r_tucker_amd import synthetic
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup = 5, 2
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+                          "--no-cpu-baseline", "--prewarm-ms", "100", "--dump-outputs", str(tmp_path)],
+                         capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stderr[-2000:]
+    rows = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(rows) == 1
+    line = json.loads(rows[0])
+    assert line["steps"] == steps and line["ms_per_step"] > 0
+    n_ent, n_rel, B = line["config"]["entities"], line["config"]["relations"], line["config"]["batch"]
+    P = np.load(tmp_path / "scores.npy")
+    idx = np.load(tmp_path / "scores_rows.npy")
+    assert P.dtype == np.float32 and idx.dtype == np.float64 and P.nbytes + idx.nbytes <= 64 << 20
+    assert P.shape == (len(idx), n_ent) and 0 < len(idx) < B and np.all(np.diff(idx) > 0)
+    core, R, S, O = [torch.from_numpy(x) for x in synthetic.make_params(n_ent, n_rel, tuple(line["config"]["rank"]), 322)]
+    h, r = synthetic.make_queries(n_ent, n_rel, B, 1000 + (warmup + steps - 1) % 64)
+    sel = idx.astype(np.int64)
+    ref = orc.score_ref(core, R, S, O, torch.from_numpy(h[sel]), torch.from_numpy(r[sel])).numpy()
+    assert np.abs(P - ref).max() < 2e-5
