@@ -86,6 +86,17 @@ typedef enum rtk_dtype {
 #define RTK_SCORE_KERNEL_WS 0x200u  /* wave-specialised persistent kernel (csrc/rtk_score_ws_kernel.h)           */
 #define RTK_SCORE_KERNEL_V3 0x300u  /* two workgroups per CU, every wave does everything (rtk_score_split_kernel.h) */
 
+/* Host-only queries of the rule rtk_score_packed_f32 follows (no device is touched; valid without a GPU), for a
+ * 16-byte-aligned O, n_local entities, object rank c <= 512 and the kernel hint bits of `flags`:
+ * rtk_score_kernel_f32 returns the RTK_SCORE_KERNEL_* value of the kernel that runs;
+ * rtk_score_fifth_group_columns_f32 returns how many of the n_local entity columns the column-group kernel computes
+ * as a K-split fifth group of its set (four K-range chains added in a fixed order instead of one chain: these scores
+ * may differ in the last bits from an entity-sharded run), and if `mask` is not NULL sets mask[j] to 1 for those
+ * columns and 0 for the others (n_local bytes).  0 unless the column-group kernel runs.  Both return
+ * RTK_ERR_BAD_ARG for shapes rtk_score_packed_f32 does not take. */
+int rtk_score_kernel_f32(int64_t n_local, int c, unsigned flags);
+int64_t rtk_score_fifth_group_columns_f32(int64_t n_local, int c, unsigned flags, unsigned char *mask);
+
 int rtk_version(void);
 const char *rtk_last_error_string(void);
 

@@ -34,6 +34,8 @@ SIGNATURES = {
     "rtk_query_vectors_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     "rtk_score_f32": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _u, _p]),
     "rtk_score_packed_f32": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _u, _p]),
+    "rtk_score_kernel_f32": (_i, [_i64, _i, _u]),
+    "rtk_score_fifth_group_columns_f32": (_i64, [_i64, _i, _u, _p]),
     "rtk_score_1vN_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _u, _p, _sz, _p]),
     "rtk_query_vectors_bf16": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _sz, _p]),
     "rtk_score_packed_bf16": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _u, _p]),

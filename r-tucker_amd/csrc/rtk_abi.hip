@@ -7,6 +7,7 @@
 
 #include "rtk_common.h"
 #include "rtk_pack.h"
+#include "rtk_score_select.h"
 
 static thread_local char g_err[512] = "";
 
@@ -21,7 +22,6 @@ int rtk_query_vectors_f32_impl(const float *core, int a, int b, int c, const flo
                                const float *S, int64_t n_sub, const int64_t *rel_idx,
                                const int64_t *sub_idx, int64_t batch, float *v_out, void *q_packed,
                                const RtkWorkspace &ws, hipStream_t st);
-int rtk_split_ksteps_supported(int c);
 int rtk_query_vectors_bf16_impl(const void *core, int a, int b, int c, const void *R, int64_t n_rel,
                                 const void *S, int64_t n_sub, const int64_t *rel_idx,
                                 const int64_t *sub_idx, int64_t batch, float *v_out, void *q_packed,
@@ -277,7 +277,7 @@ extern "C" int rtk_timer_destroy(void *timer) {
     return RTK_OK;
 }
 
-extern "C" int rtk_version(void) { return 211; }
+extern "C" int rtk_version(void) { return 212; }
 extern "C" const char *rtk_last_error_string(void) { return g_err; }
 
 extern "C" size_t rtk_workspace_bytes(int dtype, int64_t batch, int64_t n_rel, int a, int b, int c) {

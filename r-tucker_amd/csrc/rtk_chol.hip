@@ -29,7 +29,6 @@
 // the pivot's reciprocal square root comes from v_rsq_f64 + two Newton steps (every thread computes it; the IEEE sqrt and
 // division sequences were most of a column step).  The 32 x 7 sequential column steps are what is left (106 us).
 #include "rtk_common.h"
-#include <stdlib.h>
 
 namespace {
 
@@ -309,7 +308,7 @@ extern "C" int rtk_gram_factor_f64(const void *S, int64_t batch, int k, int equi
     RTK_REQUIRE(k > 0 && k <= KMAX, RTK_ERR_UNSUPPORTED, "rtk_gram_factor_f64: k=%d not in [1, %d]", k, KMAX);
     RTK_REQUIRE(S != R_out && S != X_out && R_out != X_out, RTK_ERR_BAD_ARG, "rtk_gram_factor_f64: buffers must be distinct");
     RTK_REQUIRE(shift_diag >= 0.0 && shift_trace >= 0.0, RTK_ERR_BAD_ARG, "rtk_gram_factor_f64: shifts must be >= 0");
-    static const int tune = getenv("RTK_CHOL_TUNE") ? atoi(getenv("RTK_CHOL_TUNE")) : 0;   // timing ablations (wrong results)
+    const int tune = 0;   // the kernel's phase-skipping timing ablations stay off (they give wrong results)
     hipLaunchKernelGGL(chol_inv_kernel, dim3((unsigned)batch), dim3(NT), 0, (hipStream_t)stream, (const double *)S, k,
                        equilibrate ? 1 : 0, shift_diag, shift_trace, (double *)R_out, (double *)X_out, tune);
     return rtk_check_launch("rtk_gram_factor_f64");

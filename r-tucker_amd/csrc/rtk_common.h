@@ -4,6 +4,7 @@
 #include <hip/hip_ext.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <utility>
 
 #include "rtucker_hip.h"
 
@@ -73,6 +74,21 @@ static inline int rtk_ensure_dynamic_lds(const void *kernel, int bytes, std::ato
 
 static inline size_t rtk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int64_t rtk_cdiv(int64_t x, int64_t y) { return (x + y - 1) / y; }
+
+// Runtime k-step count -> template argument: returns f(std::integral_constant<int, ks>{}) for 1 <= ks <= KMAX (f is
+// instantiated for every one of them), else RTK_ERR_UNSUPPORTED.  The packed query planes were written for exactly
+// `ks` k-steps (tile stride), so a score kernel's instantiation must match exactly.
+template <typename F, int... I>
+static inline int rtk_dispatch_ksteps_(int ks, const char *what, F &f, std::integer_sequence<int, I...>) {
+    int rc = RTK_ERR_UNSUPPORTED;
+    if (!((ks == I + 1 && ((rc = f(std::integral_constant<int, I + 1>{})), true)) || ...))
+        rtk_set_error("%s: unsupported k-step count %d", what, ks);
+    return rc;
+}
+template <int KMAX, typename F>
+static inline int rtk_dispatch_ksteps(int ks, const char *what, F &&f) {
+    return rtk_dispatch_ksteps_(ks, what, f, std::make_integer_sequence<int, KMAX>{});
+}
 
 // Workspace layout (all offsets 256-B aligned), see rtk_abi.hip::ws_layout
 struct RtkWorkspace {

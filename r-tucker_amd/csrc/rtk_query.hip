@@ -10,7 +10,6 @@
 // planes" the split-fp16 score kernel consumes (per-row power-of-two scaling and
 // hi/lo fp16 split in MFMA-fragment order; layout in rtk_pack.h).
 #include "rtk_common.h"
-#include <stdlib.h>
 #include "rtk_pack.h"
 
 namespace {
@@ -797,33 +796,21 @@ struct ContractPlan {   // host-side choices of step (2), needed before step (1)
     int QG;
     size_t smem_grouped;
 };
-constexpr size_t GROUPED16_LDS_MAX = 78 * 1024;
 static ContractPlan plan_contract(int b, int c, int64_t batch, const float *tables, int64_t n_slots) {
     ContractPlan p;
     p.cvec = (c % 4 == 0) && ((reinterpret_cast<uintptr_t>(tables) & 15) == 0);
     const int cW = p.cvec ? 4 : 1;
     const int ccols = (c + cW - 1) / cW;
-    // queries per work item (a work item reads its whole b x c table once).  16 is built for A/B only
-    // (RTK_CONTRACT_QG=16): at BASELINE configs[4] -- 8192 queries over 1000 relations, 43 % of the relations with more
-    // than eight queries, 1430 items of 8 against ~1000 of 16, 1 GB of tables -- the step was 2 % SLOWER with 16
-    // (1.441 / 1.461 ms against 1.413 / 1.428 on one box: 212 registers and 64 KB of LDS leave two workgroups per CU)
-    static const int force_qg = getenv("RTK_CONTRACT_QG") ? atoi(getenv("RTK_CONTRACT_QG")) : 0;
+    // queries per work item (a work item reads its whole b x c table once).  16 was measured and left out: at
+    // BASELINE configs[4] -- 8192 queries over 1000 relations, 43 % of the relations with more than eight queries,
+    // 1430 items of 8 against ~1000 of 16, 1 GB of tables -- the step was 2 % SLOWER with 16 (1.441 / 1.461 ms against
+    // 1.413 / 1.428 on one box: 212 registers and 64 KB of LDS leave two workgroups per CU)
     p.QG = batch >= 2048 ? 8 : 4;
-    if (force_qg == 4 || force_qg == 8 || force_qg == 16) p.QG = force_qg;
     const int ngroups = ccols <= 256 ? 256 / ccols : 1;
     const int pg = ngroups > 1 ? ngroups - 1 : 1;
     p.smem_grouped = ccols <= 256
         ? (size_t)((size_t)p.QG * ((b + 3) & ~3) + (size_t)p.QG * pg * ccols * cW) * sizeof(float) : (size_t)-1;
-    static const int force = [] {   // RTK_CONTRACT=perquery|grouped: A/B comparisons
-        const char *e = getenv("RTK_CONTRACT");
-        return !e ? 0 : (e[0] == 'p' ? 1 : (e[0] == 'g' ? 2 : 0));
-    }();
-    // (16 queries: up to 78 KB of dynamic LDS, two workgroups per CU -- opted in per instantiation in contract_stage)
-    if (p.smem_grouped != (size_t)-1 && p.smem_grouped > GROUPED16_LDS_MAX && p.QG == 16) {
-        p.QG = 8;
-        p.smem_grouped = (size_t)((size_t)p.QG * ((b + 3) & ~3) + (size_t)p.QG * pg * ccols * cW) * sizeof(float);
-    }
-    p.grouped = p.smem_grouped <= (p.QG == 16 ? GROUPED16_LDS_MAX : 64 * 1024 - 1024) && force != 1 && (batch >= 2048 || force == 2);
+    p.grouped = batch >= 2048 && p.smem_grouped <= 64 * 1024 - 1024;
     return p;
 }
 
@@ -840,14 +827,8 @@ static int contract_stage(const float *tables, int b, int c, const T *S, int64_t
         RTK_REQUIRE(have_groups, RTK_ERR_BAD_ARG, "rtk_query_vectors: grouped contract without groups");
         const unsigned nwg = (unsigned)(batch / cp.QG + (n_slots < batch ? n_slots : batch) + 8);   // upper bound on the work items, rounded up to 8 (flags[2] holds the count)
 #define RTK_CG(V_, Q_) hipLaunchKernelGGL((contract_grouped_kernel<T, V_, Q_>), dim3(nwg), dim3(256), cp.smem_grouped, st, tables, b, c, S, n_sub, rel_idx, sub_idx, (int)n_rel, grp_work, grp_order, v_out, (unsigned char *)q_packed, ksteps, flags, rel_part, rel_parts)
-        if (cp.QG == 16) {
-            static std::atomic<unsigned long long> ok_v{0}, ok_s{0};
-            const int rc = cp.cvec ? rtk_ensure_dynamic_lds(reinterpret_cast<const void *>(&contract_grouped_kernel<T, true, 16>), (int)GROUPED16_LDS_MAX, ok_v, "contract_grouped_kernel")
-                                   : rtk_ensure_dynamic_lds(reinterpret_cast<const void *>(&contract_grouped_kernel<T, false, 16>), (int)GROUPED16_LDS_MAX, ok_s, "contract_grouped_kernel");
-            if (rc != RTK_OK) return rc;
-        }
-        if (cp.cvec) { if (cp.QG == 16) RTK_CG(true, 16); else if (cp.QG == 8) RTK_CG(true, 8); else RTK_CG(true, 4); }
-        else { if (cp.QG == 16) RTK_CG(false, 16); else if (cp.QG == 8) RTK_CG(false, 8); else RTK_CG(false, 4); }
+        if (cp.cvec) { if (cp.QG == 8) RTK_CG(true, 8); else RTK_CG(true, 4); }
+        else { if (cp.QG == 8) RTK_CG(false, 8); else RTK_CG(false, 4); }
 #undef RTK_CG
         return rtk_check_launch("rtk_query_vectors");
     }
@@ -883,9 +864,8 @@ static int query_vectors_impl(const T *core, int a, int b, int c, const T *R, in
     // The slot order of the queries rides in the first kernel of the table build (one extra workgroup, no launch).  For
     // the per-query contract kernel it is only worth L2 locality (~1.8 us at B = 512), and at a small relation rank the
     // one-workgroup sort IS the tables kernel's critical path (7.4 us against ~4 without it): built there only when the
-    // table build is a GEMM (a > 32).  WN18RR per-batch step 49.0 -> 46.9 us on one box (RTK_PB_GROUPS=1 / 0 force it).
-    static const int pb_env = getenv("RTK_PB_GROUPS") ? atoi(getenv("RTK_PB_GROUPS")) : -1;
-    const bool groups = cp.grouped || (pb_env < 0 ? a > 32 : pb_env != 0);
+    // table build is a GEMM (a > 32).  WN18RR per-batch step 49.0 -> 46.9 us on one box.
+    const bool groups = cp.grouped || a > 32;
     GroupArgs ga{rel_idx, planned ? ws.slot_of_rel : nullptr, ws.grp_cnt, ws.grp_order, ws.grp_work, ws.flags,
                  (int)batch, (int)n_rel, n_u_max, groups ? cp.QG : 0, sub_idx, cp.grouped ? nullptr : ws.grp_qinfo};
     int rc = build_tables<T>(core, a, b, c, R, n_rel, planned ? ws.rel_list : nullptr, n_u_max,
@@ -913,14 +893,12 @@ static int from_tables_impl(const float *tables, int64_t n_rel, int b, int c, co
                             const int64_t *rel_idx, const int64_t *sub_idx, int64_t batch, float *v_out,
                             void *q_packed, const RtkWorkspace &ws, hipStream_t st, int rel_part = 0, int rel_parts = 1) {
     const ContractPlan cp = plan_contract(b, c, batch, tables, n_rel);
-    static const bool order_small = getenv("RTK_FT_ORDER") != nullptr;   // A/B: slot order for the per-query kernel too
-    const bool groups = cp.grouped || order_small;
-    if (groups) {
+    if (cp.grouped) {
         GroupArgs ga{rel_idx, nullptr, ws.grp_cnt, ws.grp_order, ws.grp_work, ws.flags,
-                     (int)batch, (int)n_rel, (int)n_rel, cp.QG, sub_idx, cp.grouped ? nullptr : ws.grp_qinfo};
+                     (int)batch, (int)n_rel, (int)n_rel, cp.QG, sub_idx, nullptr};
         hipLaunchKernelGGL(groups_kernel, dim3(1), dim3(1024), 0, st, ga);
     }
-    return contract_stage<T>(tables, b, c, S, n_sub, rel_idx, sub_idx, n_rel, batch, nullptr, (int)n_rel, cp, groups,
+    return contract_stage<T>(tables, b, c, S, n_sub, rel_idx, sub_idx, n_rel, batch, nullptr, (int)n_rel, cp, cp.grouped,
                              ws.grp_work, ws.grp_order, ws.grp_qinfo, ws.flags, v_out, q_packed, st, rel_part, rel_parts);
 }
 

@@ -10,16 +10,15 @@
 // of the previous tile in the MFMA gaps.  With a third of the MFMA work of the fp32 path the
 // kernel is bound by the fp32 score write (HBM).
 #include "rtk_common.h"
-#include <stdlib.h>
 #include "rtk_pack.h"
 
 #ifndef RTK_BF16_ABL
-#define RTK_BF16_ABL 0          // tools/ablate/bf16 builds only: 1 no stores, 2 no LDS fragment reads, 4 no staging, 8 no barrier,
+#define RTK_BF16_ABL 0          // A/B builds only (tools/ablate/build_flag_variant.sh): 1 no stores, 2 no LDS fragment reads, 4 no staging, 8 no barrier,
                                 // 16 every query tile stores into the first tile's rows (16 MB of scores: no HBM write stream)
 #endif
 
 #ifndef RTK_BF16_ST64
-#define RTK_BF16_ST64 0         // 1 (tools/ablate/bf16 builds only): fp32 scores of the V2 loop leave as 8-byte stores (two neighbouring
+#define RTK_BF16_ST64 0         // 1 (A/B builds, tools/ablate/build_flag_variant.sh): fp32 scores of the V2 loop leave as 8-byte stores (two neighbouring
                                 // columns of one row per lane, traded between adjacent lanes through DPP): 8 store instructions per
                                 // tile instead of 16.  Parity-correct and 4 % SLOWER at the C5 shard (1.283 / 1.279 ms against
                                 // 1.234 / 1.235 on one box): the store instruction count is not what the stores cost.
@@ -338,10 +337,9 @@ int launch_nt(const unsigned char *qp, int B, const rtk_bf16 *O, int N, int c, f
         if (rc != RTK_OK) return rc;
     }
     const int n_mt = (int)rtk_cdiv(B, 32);
-    static const int qb_kb = getenv("RTK_BF16_QB_KB") ? atoi(getenv("RTK_BF16_QB_KB")) : 3072;   // A/B: block size of the sweep
     // query tiles per block of the sweep: <= 3 MB of packed planes (C5 shard, score kernel: 0.5 MB 1.47 ms,
     // 1 MB 1.29, 1.5 MB 1.20, 2.5-6 MB 1.15-1.17, unblocked 1.18 -- small blocks reload the B fragments too often)
-    int qb = (int)(((size_t)qb_kb << 10) / tile);
+    int qb = (int)(((size_t)3 << 20) / tile);
     if (qb < 1) qb = 1;
     if (qb >= n_mt) qb = n_mt;
     else qb = (int)rtk_cdiv(n_mt, rtk_cdiv(n_mt, qb));   // equal blocks
@@ -354,32 +352,20 @@ int launch_nt(const unsigned char *qp, int B, const rtk_bf16 *O, int N, int c, f
 template <int KS, int SG, int MINW, int NW>
 int launch_one(const unsigned char *qp, int B, const rtk_bf16 *O, int N, int c, float *out, int64_t ld, bool o_vec,
                 bool obf, hipStream_t st) {
-    static const bool nts_off = getenv("RTK_NO_NT_STORES") != nullptr;
-    const bool nts = !nts_off && (ld * (obf ? 2 : 4)) % 128 == 0 && (reinterpret_cast<uintptr_t>(out) & 127) == 0;
-    static const bool v1 = getenv("RTK_BF16_V1") != nullptr;     // A/B: round 2's two-chain loop in the deep-K form
+    const bool nts = (ld * (obf ? 2 : 4)) % 128 == 0 && (reinterpret_cast<uintptr_t>(out) & 127) == 0;
+    // deep-K form (NW == 8): the V2 loop, except for the exact logistic, which keeps round 2's two-chain loop
+    constexpr bool V2 = NW == 8 && SG != 1;
     if constexpr (SG == 2) {   // bf16 scores: probabilities only (the caller checks)
         if (obf) {
             // (the same accumulation order as the fp32-score form: bf16 scores = the fp32 ones rounded, bit for bit)
-            if constexpr (NW == 8) {
-                if (!v1) {
-                    if (nts) return launch_nt<KS, SG, MINW, NW, true, true, true>(qp, B, O, N, c, out, ld, o_vec, st);
-                    return launch_nt<KS, SG, MINW, NW, false, true, true>(qp, B, O, N, c, out, ld, o_vec, st);
-                }
-            }
-            if (nts) return launch_nt<KS, SG, MINW, NW, true, true>(qp, B, O, N, c, out, ld, o_vec, st);
-            return launch_nt<KS, SG, MINW, NW, false, true>(qp, B, O, N, c, out, ld, o_vec, st);
-        }
-    }
-    if constexpr (NW == 8 && SG != 1) {   // deep-K form, fp32 scores: the V2 loop
-        if (!v1) {
-            if (nts) return launch_nt<KS, SG, MINW, NW, true, false, true>(qp, B, O, N, c, out, ld, o_vec, st);
-            return launch_nt<KS, SG, MINW, NW, false, false, true>(qp, B, O, N, c, out, ld, o_vec, st);
+            if (nts) return launch_nt<KS, SG, MINW, NW, true, true, V2>(qp, B, O, N, c, out, ld, o_vec, st);
+            return launch_nt<KS, SG, MINW, NW, false, true, V2>(qp, B, O, N, c, out, ld, o_vec, st);
         }
     }
     if constexpr (SG != 1) {   // (the exact-logistic variant keeps one form)
-        if (nts) return launch_nt<KS, SG, MINW, NW, true, false>(qp, B, O, N, c, out, ld, o_vec, st);
+        if (nts) return launch_nt<KS, SG, MINW, NW, true, false, V2>(qp, B, O, N, c, out, ld, o_vec, st);
     }
-    return launch_nt<KS, SG, MINW, NW, false, false>(qp, B, O, N, c, out, ld, o_vec, st);
+    return launch_nt<KS, SG, MINW, NW, false, false, V2>(qp, B, O, N, c, out, ld, o_vec, st);
 }
 
 template <int KS, int MINW, int NW>
@@ -420,24 +406,10 @@ extern "C" int rtk_score_packed_bf16(const void *q_packed, int64_t batch, int c,
     const rtk_bf16 *Ob = (const rtk_bf16 *)O;
     const int B = (int)batch, N = (int)n_local;
     // 8-wave workgroups (256 entities share a staged query tile) once the problem fills the chip that way
-    static const bool narrow = getenv("RTK_BF16_NARROW") != nullptr;   // A/B: 4-wave workgroups, two per CU
-    const bool wide = !narrow && ks > 16 && rtk_cdiv(N, 256) * rtk_cdiv(B, 32) >= 4 * 256;
-#define RTK_KS(K_, W_) case K_: rc = launch_shape<K_, W_>(wide, qp, B, Ob, N, c, out, ld_out, sg, o_vec, obf, st); break;
-    int rc = RTK_OK;
-    switch (ks) {
-#ifdef RTK_BF16_HARNESS_KS
-        RTK_KS(RTK_BF16_HARNESS_KS, 2)
-#else
-        RTK_KS(1, 2) RTK_KS(2, 2) RTK_KS(3, 2) RTK_KS(4, 2) RTK_KS(5, 2) RTK_KS(6, 2) RTK_KS(7, 2) RTK_KS(8, 2)
-        RTK_KS(9, 2) RTK_KS(10, 2) RTK_KS(11, 2) RTK_KS(12, 2) RTK_KS(13, 2) RTK_KS(14, 2) RTK_KS(15, 2) RTK_KS(16, 2)
-        RTK_KS(17, 2) RTK_KS(18, 2) RTK_KS(19, 2) RTK_KS(20, 2) RTK_KS(21, 2) RTK_KS(22, 2) RTK_KS(23, 2) RTK_KS(24, 2)
-        RTK_KS(25, 2) RTK_KS(26, 2) RTK_KS(27, 2) RTK_KS(28, 2) RTK_KS(29, 2) RTK_KS(30, 2) RTK_KS(31, 2) RTK_KS(32, 2)
-#endif
-        default:
-            rtk_set_error("rtk_score_packed_bf16: unsupported k-step count %d", ks);
-            return RTK_ERR_UNSUPPORTED;
-    }
-#undef RTK_KS
+    const bool wide = ks > 16 && rtk_cdiv(N, 256) * rtk_cdiv(B, 32) >= 4 * 256;
+    const int rc = rtk_dispatch_ksteps<32>(ks, "rtk_score_packed_bf16", [&](auto K) {
+        return launch_shape<K.value, 2>(wide, qp, B, Ob, N, c, out, ld_out, sg, o_vec, obf, st);
+    });
     if (rc != RTK_OK) return rc;
     return rtk_check_launch("rtk_score_packed_bf16");
 }

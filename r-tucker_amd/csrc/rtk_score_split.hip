@@ -16,14 +16,21 @@
 // A fragments (conflict-free ds_read_b128) and issues 3*KS MFMAs into one 32x32
 // accumulator, and the epilogue unscales, applies the logistic and stores
 // 128-B-contiguous row segments (lane = entity) straight from the accumulator.
-#include <stdlib.h>
+#include <string.h>
 
 #include "rtk_common.h"
 #include "rtk_pack.h"
+#include "rtk_score_select.h"
 
 #include "rtk_score_split_kernel.h"
 using rtk_split::score_split_kernel;
 namespace {
+
+// Minimum resident waves per SIMD of the instantiation: two 4-wave workgroups per CU up to c = 256; for
+// 256 < c <= 512 (the doubled-rank tensors the Riemannian gradient scores) one, the hi/lo B
+// fragments take up to 256 of a wave's 512 registers (the compiler places them in the accumulation half of the
+// unified file)
+constexpr int min_waves(int ks) { return ks <= 16 ? 2 : 1; }
 
 template <int KS, int SG, int MINW>
 int launch_one(const unsigned char *qp, int B, const float *O, int N, int c, float *out, int64_t ld,
@@ -46,7 +53,7 @@ int launch_ks(const unsigned char *qp, int B, const float *O, int N, int c, floa
     // one block per resident slot (256 CUs x MINW workgroups); the kernel splits the
     // linearised (entity tile, query tile) space evenly over them
     const int64_t units = rtk_cdiv(N, 128) * rtk_cdiv(B, 32);
-    const unsigned grid = (unsigned)(units < 256 * MINW ? units : 256 * MINW);
+    const unsigned grid = (unsigned)(units < RTK_N_CU * MINW ? units : RTK_N_CU * MINW);
     if (sigmoid == 0) return launch_one<KS, 0, MINW>(qp, B, O, N, c, out, ld, o_vec, grid, st);
     if (sigmoid == 1) return launch_one<KS, 1, MINW>(qp, B, O, N, c, out, ld, o_vec, grid, st);
     return launch_one<KS, 2, MINW>(qp, B, O, N, c, out, ld, o_vec, grid, st);
@@ -64,42 +71,13 @@ int launch_loss(const unsigned char *qp, int B, const float *O, int N, int c, fl
         if (rc != RTK_OK) return rc;
     }
     const int64_t units = rtk_cdiv(N, 128) * rtk_cdiv(B, 32);
-    const unsigned grid = (unsigned)(units < 256 * MINW ? units : 256 * MINW);
+    const unsigned grid = (unsigned)(units < RTK_N_CU * MINW ? units : RTK_N_CU * MINW);
     hipLaunchKernelGGL((score_split_kernel<KS, 2, MINW, 0, true>), dim3(grid), dim3(256), smem, st, qp, B, O, N, c, out, ld,
                        o_vec, t0, partials);
     return RTK_OK;
 }
 
 }  // namespace
-
-int rtk_score_ws_launch(const unsigned char *qp, int B, const float *O, int N, int c, float *out, int64_t ld,
-                        int sg, bool o_vec, hipStream_t st);
-
-int rtk_score_cg_launch(const unsigned char *qp, int B, const float *O, int N, int c, float *out, int64_t ld,
-                        int sg, bool o_vec, bool force, hipStream_t st);
-
-// Default: the column-group kernel (cg) where its schedule fills the chip (rtk_score_cg.hip), else the
-// persistent wave-specialised kernel (ws), then the two-workgroups-per-CU kernel (v3) for the shapes
-// neither covers.  RTK_SCORE_KERNEL=v3 forces v3, =ws skips cg, =cg runs cg on every shape it can
-// (c <= 208) -- A/B comparisons and tests.  (The two-tiles-per-barrier variant "ws2" was measured
-// slower, 53.9 vs 48.5 us at the WN18RR shape, and lives in tools/ablate/ only.)
-// 0 = v3 only, 1 = ws then v3, 2 = cg (by shape) then ws then v3, 3 = cg (forced) then ws then v3
-static int kernel_choice() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("RTK_SCORE_KERNEL");
-        if (e && e[0] == 'v' && e[1] == '3') v = 0;
-        else if (e && e[0] == 'w' && e[1] == 's') v = 1;
-        else if (e && e[0] == 'c' && e[1] == 'g') v = 3;
-        else v = 2;
-    }
-    return v;
-}
-
-int rtk_split_ksteps_supported(int c) {
-    const int ks = (c + 15) / 16;
-    return ks >= 1 && ks <= 32;   // two fp16 planes of B fragments must fit the register file next to the pipeline state
-}
 
 extern "C" int rtk_score_packed_f32(const void *q_packed, int64_t batch, int c, const float *O,
                                     int64_t n_local, float *out, int64_t ld_out, unsigned flags,
@@ -116,39 +94,56 @@ extern "C" int rtk_score_packed_f32(const void *q_packed, int64_t batch, int c, 
     const bool o_vec = (c % 4 == 0) && ((reinterpret_cast<uintptr_t>(O) & 15) == 0);
     const int B = (int)batch, N = (int)n_local;
     const unsigned char *qp = (const unsigned char *)q_packed;
-    const unsigned hint = flags & RTK_SCORE_KERNEL_MASK;
-    const int choice = hint == RTK_SCORE_KERNEL_CG ? 3 : hint == RTK_SCORE_KERNEL_WS ? 1 : hint == RTK_SCORE_KERNEL_V3 ? 0
-                                                                                                        : kernel_choice();
-    if (choice >= 2) {
-        const int took = rtk_score_cg_launch(qp, B, O, N, c, out, ld_out, sg, o_vec, choice == 3, st);
-        if (took < 0) return took;
-        if (took) return rtk_check_launch("rtk_score_packed_f32");
+    const RtkScorePlan plan = rtk_score_plan_f32(N, c, o_vec, flags);
+    int rc;
+    switch (plan.kernel) {
+    case RTK_SCORE_KERNEL_CG:
+        rc = sg == 0   ? rtk_score_cg_launch<0>(qp, B, O, N, c, out, ld_out, plan, st)
+             : sg == 1 ? rtk_score_cg_launch<1>(qp, B, O, N, c, out, ld_out, plan, st)
+                       : rtk_score_cg_launch<2>(qp, B, O, N, c, out, ld_out, plan, st);
+        break;
+    case RTK_SCORE_KERNEL_WS: rc = rtk_score_ws_launch(qp, B, O, N, c, out, ld_out, sg, st); break;
+    default:
+        rc = rtk_dispatch_ksteps<32>(ks, "rtk_score_packed_f32", [&](auto K) {
+            return launch_ks<K.value, min_waves(K.value)>(qp, B, O, N, c, out, ld_out, sg, o_vec, st);
+        });
     }
-    if (choice >= 1) {
-        const int took = rtk_score_ws_launch(qp, B, O, N, c, out, ld_out, sg, o_vec, st);
-        if (took < 0) return took;
-        if (took) return rtk_check_launch("rtk_score_packed_f32");
-    }
-    int rc = RTK_OK;
-    // the packed planes were written for exactly `ks` k-steps (tile stride), so the
-    // instantiation must match exactly.
-#define RTK_KS(K_, W_) \
-    case K_: rc = launch_ks<K_, W_>(qp, B, O, N, c, out, ld_out, sg, o_vec, st); break;
-    switch (ks) {
-        RTK_KS(1, 2) RTK_KS(2, 2) RTK_KS(3, 2) RTK_KS(4, 2) RTK_KS(5, 2) RTK_KS(6, 2) RTK_KS(7, 2) RTK_KS(8, 2)
-        RTK_KS(9, 2) RTK_KS(10, 2) RTK_KS(11, 2) RTK_KS(12, 2) RTK_KS(13, 2) RTK_KS(14, 2) RTK_KS(15, 2) RTK_KS(16, 2)
-        // 256 < c <= 512 (the doubled-rank tensors the Riemannian gradient scores): one
-        // 4-wave workgroup per CU, the hi/lo B fragments take up to 256 of a wave's 512 registers
-        // (the compiler places them in the accumulation half of the unified file)
-        RTK_KS(17, 1) RTK_KS(18, 1) RTK_KS(19, 1) RTK_KS(20, 1) RTK_KS(21, 1) RTK_KS(22, 1) RTK_KS(23, 1) RTK_KS(24, 1)
-        RTK_KS(25, 1) RTK_KS(26, 1) RTK_KS(27, 1) RTK_KS(28, 1) RTK_KS(29, 1) RTK_KS(30, 1) RTK_KS(31, 1) RTK_KS(32, 1)
-        default:
-            rtk_set_error("rtk_score_packed_f32: unsupported k-step count %d", ks);
-            return RTK_ERR_UNSUPPORTED;
-    }
-#undef RTK_KS
     if (rc != RTK_OK) return rc;
     return rtk_check_launch("rtk_score_packed_f32");
+}
+
+// Host-only queries of the plan above, for a 16-byte-aligned O (no device is touched).
+static int query_plan(const char *what, int64_t n_local, int c, unsigned flags, RtkScorePlan *plan) {
+    RTK_REQUIRE(n_local > 0 && n_local < (1ll << 31) - 256 && rtk_split_ksteps_supported(c), RTK_ERR_BAD_ARG,
+                "%s: n_local=%lld c=%d outside the split-fp16 kernels' shapes", what, (long long)n_local, c);
+    *plan = rtk_score_plan_f32(n_local, c, c % 4 == 0, flags);
+    return RTK_OK;
+}
+
+extern "C" int rtk_score_kernel_f32(int64_t n_local, int c, unsigned flags) {
+    RtkScorePlan plan;
+    const int rc = query_plan("rtk_score_kernel_f32", n_local, c, flags, &plan);
+    return rc != RTK_OK ? rc : (int)plan.kernel;
+}
+
+extern "C" int64_t rtk_score_fifth_group_columns_f32(int64_t n_local, int c, unsigned flags, unsigned char *mask) {
+    RtkScorePlan plan;
+    const int rc = query_plan("rtk_score_fifth_group_columns_f32", n_local, c, flags, &plan);
+    if (rc != RTK_OK) return rc;
+    if (mask) memset(mask, 0, (size_t)n_local);
+    if (plan.kernel != RTK_SCORE_KERNEL_CG) return 0;
+    // set u of U holds groups [G u / U, G (u + 1) / U) (rtk_score_cg_kernel.h, Geo::first_group); a set of five
+    // computes its fifth group as four K-range chains
+    const int64_t G = rtk_cdiv(n_local, 32), U = plan.U;
+    int64_t cols = 0;
+    for (int64_t u = 0; u < U; ++u) {
+        const int64_t gb = G * u / U, ge = G * (u + 1) / U;
+        if (ge - gb != RTK_CG_GROUPS_PER_SET) continue;
+        const int64_t j0 = (gb + 4) * 32, j1 = (gb + 5) * 32 < n_local ? (gb + 5) * 32 : n_local;
+        if (mask) memset(mask + j0, 1, (size_t)(j1 - j0));
+        cols += j1 - j0;
+    }
+    return cols;
 }
 
 extern "C" int rtk_score_bce_partials(void) { return 512; }      // >= the largest grid of the loss kernel
@@ -173,19 +168,9 @@ extern "C" int rtk_score_packed_bce_f32(const void *q_packed, int64_t batch, int
     const int B = (int)batch, N = (int)n_local;
     const float t0 = label_smoothing / (float)n_local;
     const unsigned char *qp = (const unsigned char *)q_packed;
-    int rc = RTK_OK;
-#define RTK_KS(K_, W_) \
-    case K_: rc = launch_loss<K_, W_>(qp, B, O, N, c, x_out, ld_out, o_vec, t0, partials_out, st); break;
-    switch (ks) {
-        RTK_KS(1, 2) RTK_KS(2, 2) RTK_KS(3, 2) RTK_KS(4, 2) RTK_KS(5, 2) RTK_KS(6, 2) RTK_KS(7, 2) RTK_KS(8, 2)
-        RTK_KS(9, 2) RTK_KS(10, 2) RTK_KS(11, 2) RTK_KS(12, 2) RTK_KS(13, 2) RTK_KS(14, 2) RTK_KS(15, 2) RTK_KS(16, 2)
-        RTK_KS(17, 1) RTK_KS(18, 1) RTK_KS(19, 1) RTK_KS(20, 1) RTK_KS(21, 1) RTK_KS(22, 1) RTK_KS(23, 1) RTK_KS(24, 1)
-        RTK_KS(25, 1) RTK_KS(26, 1) RTK_KS(27, 1) RTK_KS(28, 1) RTK_KS(29, 1) RTK_KS(30, 1) RTK_KS(31, 1) RTK_KS(32, 1)
-        default:
-            rtk_set_error("rtk_score_packed_bce_f32: unsupported k-step count %d", ks);
-            return RTK_ERR_UNSUPPORTED;
-    }
-#undef RTK_KS
+    const int rc = rtk_dispatch_ksteps<32>(ks, "rtk_score_packed_bce_f32", [&](auto K) {
+        return launch_loss<K.value, min_waves(K.value)>(qp, B, O, N, c, x_out, ld_out, o_vec, t0, partials_out, st);
+    });
     if (rc != RTK_OK) return rc;
     return rtk_check_launch("rtk_score_packed_bce_f32");
 }

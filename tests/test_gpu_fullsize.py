@@ -11,7 +11,6 @@ seconds to minutes at these sizes, so only samples are evaluated exactly):
   the exact-fp32 MFMA GEMM are three independent implementations of the same product;
 * sampled entries against the float64 oracle.
 """
-import os
 
 import numpy as np
 import pytest
@@ -66,27 +65,22 @@ def test_c2_wn18rr_full_size_properties(rt, monkeypatch):
     assert torch.allclose(p.double().sum(1), torch.sigmoid(z.double()).sum(1), rtol=1e-6)
 
 
-def test_c2_kernels_agree_v3_vs_ws():
-    """Same inputs through the three split-fp16 kernels (selected by RTK_SCORE_KERNEL at first use, so
-    each runs in a child process, one after the other)."""
-    import subprocess
-    import sys
-    code = r'''
-import sys, os, numpy as np, torch
-sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests", "golden"))
-import gen, r_tucker_amd as rt
-core, R, S, O = [torch.from_numpy(x).cuda() for x in gen.make_params(40943, 22, (10, 200, 200), 322)]
-h, r = [torch.from_numpy(x).cuda() for x in gen.make_queries(40943, 22, 512, 77)]
-z = rt.score_1vN(core, R, S, O, h, r, sigmoid=False)
-print(float(z.double().sum()), float(z.double().abs().sum()), float(z[17, 4093]), float(z[511, 40942]))
-'''
+def test_c2_kernels_agree_v3_vs_ws(rt):
+    """Same inputs through the three split-fp16 kernels (rtk_score_1vN_f32 with each kernel hint)."""
+    L = rt._lib
+    lib = L.load()
+    n_ent, n_rel, B, (a, b, c) = 40943, 22, 512, (10, 200, 200)
+    core, R, S, O = [torch.from_numpy(x).cuda() for x in gen.make_params(n_ent, n_rel, (a, b, c), 322)]
+    h, r = [torch.from_numpy(x).cuda() for x in gen.make_queries(n_ent, n_rel, B, 77)]
+    ws = torch.zeros(lib.rtk_workspace_bytes(L.RTK_F32, B, n_rel, a, b, c), dtype=torch.uint8, device="cuda")
     outs = []
-    for k in ("cg", "ws", "v3"):
-        env = dict(os.environ, RTK_SCORE_KERNEL=k)
-        res = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, env=env,
-                             cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))), timeout=300)
-        assert res.returncode == 0, res.stderr[-2000:]
-        outs.append([float(x) for x in res.stdout.strip().split()[-4:]])
+    for hint in (L.RTK_SCORE_KERNEL_CG, L.RTK_SCORE_KERNEL_WS, L.RTK_SCORE_KERNEL_V3):
+        z = torch.empty((B, n_ent), dtype=torch.float32, device="cuda")
+        L.check(lib.rtk_score_1vN_f32(core.data_ptr(), a, b, c, R.data_ptr(), n_rel, S.data_ptr(), n_ent, O.data_ptr(),
+                                      n_ent, r.data_ptr(), h.data_ptr(), B, z.data_ptr(), n_ent, hint, ws.data_ptr(),
+                                      ws.numel(), torch.cuda.current_stream().cuda_stream), "rtk_score_1vN_f32")
+        torch.cuda.synchronize()
+        outs.append([float(z.double().sum()), float(z.double().abs().sum()), float(z[17, 4093]), float(z[511, 40942])])
     a = outs[0]
     for b in outs[1:]:
         assert abs(a[0] - b[0]) <= 1e-6 * a[1] and abs(a[2] - b[2]) <= 2e-5 * (1 + abs(a[2])) and abs(a[3] - b[3]) <= 2e-5 * (1 + abs(a[3]))

@@ -43,22 +43,6 @@ def _score(rt, qp, B, O, flags, pitch=None, fill=None):
     return buf
 
 
-def _fifth_group_columns(N, W_max=256):
-    """columns that the cg schedule puts into a set's fifth (K-split) group"""
-    G = -(-N // 32)
-    sets = -(-G // 5)
-    if sets < W_max:
-        sets = min(G, W_max)
-    W = min(W_max, sets)
-    U = W * -(-sets // W)
-    fifth = np.zeros(N, dtype=bool)
-    for u in range(U):
-        gb, ge = G * u // U, G * (u + 1) // U
-        if ge - gb == 5:
-            fifth[(gb + 4) * 32:min(N, (gb + 5) * 32)] = True
-    return fifth
-
-
 SHAPES = [
     # (N, c, B, pitch)                      what it exercises (sets: ceil(G / 5) of them when that fills 256 workgroups,
     #                                       else min(G, 256) sets of 1-5 groups)
@@ -97,7 +81,7 @@ def test_all_kernels_against_float64(rt, N, c, B, pitch):
         err = np.max(np.abs(out[name] - z64) / (Z_TOL * (1 + np.abs(z64)) + nb))
         print(f"{name}: max |dz| / (2e-5 (1+|z|) + normwise bound) = {err:.2e}")
         assert err <= 1.0, name
-    fifth = _fifth_group_columns(N)
+    fifth = rt.ops.cg_fifth_group_columns(N, c, L.RTK_SCORE_KERNEL_CG)
     assert np.array_equal(out["cg"][:, ~fifth], out["ws"][:, ~fifth]), "register groups must equal the ws kernel bit for bit"
     if fifth.any():
         d = np.abs(out["cg"][:, fifth] - out["ws"][:, fifth]) / (1 + np.abs(z64[:, fifth]))
@@ -120,8 +104,10 @@ def test_default_dispatch_takes_cg_at_the_wn18rr_shape(rt):
     between the two; up to 1024 groups (N = 20 000, 14 951) the cg kernel has the ws kernel's bits everywhere."""
     g = torch.Generator().manual_seed(11)
     L = rt._lib
+    lib = L.load()
     for N in (40943, 20000, 14951, 46000, 100000):
-        fifth = bool(_fifth_group_columns(N).any())
+        fifth_cg = rt.ops.cg_fifth_group_columns(N, 200, L.RTK_SCORE_KERNEL_CG)
+        fifth = bool(fifth_cg.any())
         assert fifth == (N in (40943, 100000))
         v = torch.randn((64, 200), generator=g).cuda()
         O = torch.randn((N, 200), generator=g).cuda()
@@ -130,6 +116,7 @@ def test_default_dispatch_takes_cg_at_the_wn18rr_shape(rt):
         cg = _score(rt, qp, 64, O, L.RTK_SCORE_KERNEL_CG).cpu().numpy()
         ws = _score(rt, qp, 64, O, L.RTK_SCORE_KERNEL_WS).cpu().numpy()
         assert np.array_equal(cg, ws) == (not fifth)
-        assert np.array_equal(cg[:, ~_fifth_group_columns(N)], ws[:, ~_fifth_group_columns(N)])
+        assert np.array_equal(cg[:, ~fifth_cg], ws[:, ~fifth_cg])
         assert np.array_equal(auto, ws if N > 40960 else cg)
+        assert lib.rtk_score_kernel_f32(N, 200, 0) == (L.RTK_SCORE_KERNEL_CG if 18432 <= N <= 40960 else L.RTK_SCORE_KERNEL_WS)
         assert bool(rt.ops.cg_fifth_group_columns(N, 200).any()) == (fifth and N <= 40960)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Time rtk_gram_factor_f64 (csrc/rtk_chol.hip) on k x k Gram matrices: us per launch for a batch of 1 and of 4, and the
-error of the factor against float64 torch.   usage: tools/chol_timing.py [k]      (RTK_CHOL_TUNE: phase ablations)"""
+error of the factor against float64 torch.   usage: tools/chol_timing.py [k]"""
 import os
 import sys
 
@@ -32,4 +32,4 @@ for nb in (1, 4):
     torch.cuda.synchronize()
     err_r = ((R.transpose(1, 2) @ R - S).abs().max() / S.abs().max()).item()
     err_x = ((X.transpose(1, 2) @ S @ X - torch.eye(k, dtype=torch.float64, device="cuda")).abs().max()).item()
-    print(f"k {k} batch {nb}: {e0.elapsed_time(e1) / 50 * 1e3:.1f} us per launch   |R^T R - S| / |S| = {err_r:.1e}   |X^T S X - I| = {err_x:.1e}   tune {os.environ.get('RTK_CHOL_TUNE', '0')}")
+    print(f"k {k} batch {nb}: {e0.elapsed_time(e1) / 50 * 1e3:.1f} us per launch   |R^T R - S| / |S| = {err_r:.1e}   |X^T S X - I| = {err_x:.1e}")

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Wall time of the evaluation tail (score kernel -> filtered-rank kernel over the score matrix) on WN18RR test queries
-with seeded parameters: does a cache policy of the score stores cost the consumer anything?  RTK_WS_NT=0|1."""
+with seeded parameters."""
 import os
 import sys
 import time
@@ -28,5 +28,5 @@ n = 20
 for _ in range(n):
     m, _ = rt.evaluate(model, test_set, batch_size=512)
 torch.cuda.synchronize()
-print(f"RTK_WS_NT={os.environ.get('RTK_WS_NT', 'default')}: evaluate() over {len(test_set.features)} test queries: "
+print(f"evaluate() over {len(test_set.features)} test queries: "
       f"{(time.perf_counter() - t0) / n * 1e3:.2f} ms per pass, MRR {m['mrr']:.6f}")
