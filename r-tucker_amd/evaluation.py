@@ -156,16 +156,15 @@ class _EvalPlan:
     ranks, BCE row sums, packed query planes, running sums."""
 
     def __init__(self, B, N, c, n_rel, dtype, device):
-        from .ops import alloc_scores
+        from .ops import _dtype_code, alloc_scores
         lib = _lib.load()
-        bf16 = dtype == torch.bfloat16
-        self.dcode = _lib.RTK_BF16 if bf16 else _lib.RTK_F32
         self.P = alloc_scores(B, N, device)
         self.ld = self.P.stride(0) if B > 1 else N
         self.ranks = torch.empty(B, dtype=torch.int32, device=device)
         self.bce = torch.empty(B, dtype=torch.float64, device=device)
         self.acc = torch.zeros(5, dtype=torch.float64, device=device)
-        self.qp = torch.empty(lib.rtk_packed_query_bytes(self.dcode, B, c), dtype=torch.uint8, device=device)
+        self.qp = torch.empty(lib.rtk_packed_query_bytes(_dtype_code(dtype == torch.bfloat16), B, c), dtype=torch.uint8,
+                              device=device)
         self.ws_bytes = lib.rtk_from_tables_workspace_bytes(B, n_rel)
 
 
@@ -190,7 +189,8 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
     O = S if sym else model.O.weight.data
     n = len(dataset)
     a, b, c = core.shape
-    if (b != c or core.dtype not in (torch.float32, torch.bfloat16) or c > 512 or not core.is_cuda
+    if (b != c or core.dtype not in (torch.float32, torch.bfloat16) or not ops._packed_stage2(c, exact=False)
+            or not core.is_cuda
             or any(t.dtype != core.dtype or t.device != core.device or not t.is_contiguous() for t in (R, S, O))):
         return _evaluate_generic(model, dataset, batch_size, device, flt)      # (raises what the closure raises)
     lib = _lib.load()
@@ -203,9 +203,9 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
     tables = model._cached_tables(core, R) if hasattr(model, "_cached_tables") else None
     if tables is None:
         tables = ops.relation_tables(core, R)
-    ft = lib.rtk_query_vectors_from_tables_bf16 if bf16 else lib.rtk_query_vectors_from_tables_f32
-    sp_fn = lib.rtk_score_packed_bf16 if bf16 else lib.rtk_score_packed_f32
-    sflags = _lib.RTK_SCORE_SIGMOID | (_lib.RTK_SCORE_SIGMOID_FAST if ops.DEFAULT_SIGMOID == "fast" else 0)
+    ft = ops._entry("rtk_query_vectors_from_tables", bf16)
+    sp_fn = ops._entry("rtk_score_packed", bf16)
+    sflags = ops._score_flags(True, None, torch.float32, bf16)
     with torch.cuda.device(device):
         sp = torch.cuda.current_stream(device).cuda_stream
         ws = ops._workspace(device, sp, plan.ws_bytes)

@@ -40,11 +40,16 @@ BACKWARD_GEMM = os.environ.get("R_TUCKER_AMD_BWD_GEMM", "split_fp16")
 FUSED_BCE = os.environ.get("R_TUCKER_AMD_FUSED_BCE", "1") == "1"
 
 
+def _row_pitch(N, dtype):
+    """Row pitch, in elements, of a fresh score buffer of N columns: rows start on 128-byte boundaries (ROW_ALIGN
+    float32 elements; twice as many bf16 ones)."""
+    unit = ROW_ALIGN * (4 // dtype.itemsize) if ROW_ALIGN > 1 else 1
+    return -(-N // unit) * unit
+
+
 def alloc_scores(B, N, device, lead=(), dtype=torch.float32):
-    """(lead..., B, N) score buffer whose rows start on 128-byte boundaries (ROW_ALIGN float32
-    elements; twice as many bf16 ones)."""
-    unit = ROW_ALIGN * (4 // torch.empty((), dtype=dtype).element_size()) if ROW_ALIGN > 1 else 1
-    pitch = -(-N // unit) * unit
+    """(lead..., B, N) score buffer whose rows start on 128-byte boundaries (``_row_pitch``)."""
+    pitch = _row_pitch(N, dtype)
     buf = torch.empty(tuple(lead) + (B, pitch), dtype=dtype, device=device)
     return buf[..., :N] if pitch != N else buf
 
@@ -66,10 +71,6 @@ def _operand(name, t, dtype):
     return t.contiguous()
 
 
-def _f32c(name, t):
-    return _operand(name, t, torch.float32)
-
-
 def _idx(name, t, device):
     if isinstance(t, torch.Tensor) and t.dtype == torch.int64 and t.device == device and t.dim() == 1 and t.is_contiguous():
         return t
@@ -80,8 +81,70 @@ def _idx(name, t, device):
     return t.to(device=device, dtype=torch.int64).contiguous().view(-1)
 
 
+def _dtype_code(bf16):
+    return _lib.RTK_BF16 if bf16 else _lib.RTK_F32
+
+
+def _entry(name, bf16):
+    """The bf16 or the f32 form of a C-ABI entry point (``name_bf16`` / ``name_f32``)."""
+    return getattr(_lib.load(), name + ("_bf16" if bf16 else "_f32"))
+
+
+class _Operands:
+    """The checked operands of one call: core (a, b, c), R and, when given, S, O and the index vectors h, r of B queries;
+    contiguous, on one GPU, in one dtype, with matching widths (the C ABI takes a, b, c from the core alone)."""
+    __slots__ = ("core", "R", "S", "O", "h", "r", "a", "b", "c", "B", "dev", "bf16", "dcode")
+
+    def __init__(self, core, R, S=None, O=None, subject_idx=None, relation_idx=None):
+        _require_gpu("core", core)
+        dt = core.dtype
+        if dt not in (torch.float32, torch.bfloat16):
+            raise RuntimeError(f"core must be float32 or bfloat16, got {dt}")
+        self.bf16 = dt == torch.bfloat16
+        self.dcode = _dtype_code(self.bf16)
+        self.core = core = core.contiguous()
+        self.R = R = _operand("R", R, dt)
+        self.S = S = None if S is None else _operand("S", S, dt)
+        self.O = O = None if O is None else _operand("O", O, dt)
+        self.dev = dev = core.device
+        for n, t in (("R", R), ("S", S), ("O", O)):
+            if t is not None and t.device != dev:
+                raise RuntimeError(f"{n} is on {t.device}, core on {dev}")
+        if core.dim() != 3 or R.dim() != 2 or (S is not None and S.dim() != 2) or (O is not None and O.dim() != 2):
+            raise RuntimeError("expected core (a,b,c), R (nR,a), S (N,b), O (N,c)")
+        self.a, self.b, self.c = a, b, c = core.shape
+        if R.shape[1] != a or (S is not None and S.shape[1] != b) or (O is not None and O.shape[1] != c):
+            raise RuntimeError("factor widths " + ", ".join(f"{n} {t.shape[1]}" for n, t in (("R", R), ("S", S), ("O", O))
+                                                            if t is not None) + f" do not match core {tuple(core.shape)}")
+        self.h = self.r = None
+        self.B = 0
+        if subject_idx is not None:
+            self.h, self.r = _idx("subject_idx", subject_idx, dev), _idx("relation_idx", relation_idx, dev)
+            if self.h.numel() != self.r.numel():
+                raise RuntimeError(f"subject_idx has {self.h.numel()} entries, relation_idx {self.r.numel()}")
+            self.B = self.h.numel()
+        if b != c:
+            # asymmetric/R_TuckER.py:46: .view(-1, b) of a (B,1,c) tensor
+            raise RuntimeError(f"shape '[-1, {b}]' is invalid for input of size {self.B * c}" if self.h is not None
+                               else f"subject rank {b} must equal object rank {c} (asymmetric/R_TuckER.py:46)")
+
+    def workspace(self, sp, tables=None):
+        """The workspace of a stage 1 on stream ``sp``, from the relation ``tables`` when given, else from the core."""
+        n_rel = self.R.shape[0]
+        need = (_size("rtk_from_tables_workspace_bytes", self.B, n_rel) if tables is not None
+                else _size("rtk_workspace_bytes", self.dcode, self.B, n_rel, self.a, self.b, self.c))
+        return _workspace(self.dev, sp, need)
+
+    def check_tables(self, tables):
+        n_rel = self.R.shape[0]
+        if (not isinstance(tables, torch.Tensor) or tables.dtype != torch.float32 or tables.device != self.dev
+                or tuple(tables.shape) != (n_rel, self.b, self.c) or not tables.is_contiguous()):
+            raise RuntimeError(f"tables must be a contiguous float32 ({n_rel}, {self.b}, {self.c}) tensor on {self.dev} "
+                               "(ops.relation_tables)")
+
+
 _sizes = {}      # memoised size queries of the C ABI (one ctypes call each otherwise, per scoring call)
-_packed = {}     # (device index, stream) -> packed-query-plane buffer of the no-autograd path
+_packed = {}     # (device index, stream) -> packed-query-plane buffer of the calls that do not hand the planes out
 
 
 def _size(fn_name, *args):
@@ -157,7 +220,7 @@ def _check_now(ws, sp):
         raise IndexError("index out of range in self (subject_idx / relation_idx)")
 
 
-def _strict_check(dev, ws, sp):
+def _strict_check(ws, sp):
     if INDEX_CHECK == "strict" and not torch.cuda.is_current_stream_capturing():
         _check_now(ws, sp)
 
@@ -166,64 +229,86 @@ def _stream_ptr(device):
     return torch.cuda.current_stream(device).cuda_stream
 
 
+# Largest object rank c of the score kernels on packed query planes (rtk_score_packed_*; the library's own rule is
+# rtk_split_ksteps_supported, csrc/rtk_score_select.h).  Above it, and for exact=True, stage 2 is the exact-fp32
+# rtk_score_f32 on the unpacked query vectors, which exists for fp32 operands only.
+_PACKED_MAX_C = 512
+
+
+def _packed_stage2(c, exact):
+    """Whether the score kernel can run on packed query planes."""
+    return not exact and c <= _PACKED_MAX_C
+
+
+def _score_flags(sigmoid, sigmoid_mode, out_dtype, bf16):
+    """The score kernel's flags (logistic, its mode, bf16 output) for scores in ``out_dtype``."""
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
+    mode = sigmoid_mode or DEFAULT_SIGMOID
+    if mode not in ("fast", "exact"):
+        raise ValueError(f"sigmoid mode must be 'fast' or 'exact', got {mode!r}")
+    flags = (_lib.RTK_SCORE_SIGMOID | (_lib.RTK_SCORE_SIGMOID_FAST if mode == "fast" else 0)) if sigmoid else 0
+    if out_dtype == torch.bfloat16:
+        if not bf16 or not sigmoid or mode != "fast":
+            raise RuntimeError("bfloat16 scores: bf16 operands, sigmoid=True and the fast logistic (sigmoid_mode='fast')")
+        flags |= _lib.RTK_SCORE_OUT_BF16
+    return flags
+
+
+def _stage1(op, sp, tables, v, qp):
+    """Stage 1: the query vectors into ``v`` (B, c) fp32 and / or their packed planes into ``qp`` (either may be None),
+    from the relation ``tables`` when given, else from the core.  Returns the workspace (the error word's holder)."""
+    n_rel = op.R.shape[0]
+    vp, qpp = (None if v is None else v.data_ptr()), (None if qp is None else qp.data_ptr())
+    ws = op.workspace(sp, tables)
+    if tables is not None:
+        op.check_tables(tables)
+        _lib.check(_entry("rtk_query_vectors_from_tables", op.bf16)(
+            tables.data_ptr(), n_rel, op.b, op.c, op.S.data_ptr(), op.S.shape[0], op.r.data_ptr(), op.h.data_ptr(), op.B,
+            vp, qpp, ws.data_ptr(), ws.numel(), sp), "rtk_query_vectors_from_tables")
+    else:
+        _lib.check(_entry("rtk_query_vectors", op.bf16)(
+            op.core.data_ptr(), op.a, op.b, op.c, op.R.data_ptr(), n_rel, op.S.data_ptr(), op.S.shape[0],
+            op.r.data_ptr(), op.h.data_ptr(), op.B, vp, qpp, ws.data_ptr(), ws.numel(), sp), "rtk_query_vectors")
+    return ws
+
+
+def _stage2(bf16, sp, v, qp, O, out, flags):
+    """Stage 2: the scores ``out`` (B, N) against ``O`` from the packed planes ``qp``, or, when there are none, from
+    ``v`` (``rtk_score_f32``, which takes the sigmoid flag alone)."""
+    B, N = out.shape
+    ld = out.stride(0) if B > 1 else N
+    if qp is not None:
+        _lib.check(_entry("rtk_score_packed", bf16)(qp.data_ptr(), B, O.shape[1], O.data_ptr(), N, out.data_ptr(), ld,
+                                                    flags, sp), "rtk_score_packed")
+    else:
+        _lib.check(_lib.load().rtk_score_f32(v.data_ptr(), B, O.shape[1], O.data_ptr(), N, out.data_ptr(), ld,
+                                             flags & _lib.RTK_SCORE_SIGMOID, sp), "rtk_score_f32")
+
+
 def relation_tables(core, R):
     """``tables[u] = G x_0 R[u]`` for ALL relations -> ``(n_rel, b, c)`` fp32: the part of stage 1 that only
     depends on the parameters (einsum of asymmetric/R_TuckER.py:45 applied to every relation row).  Pass the
     result as ``tables=`` to ``score_1vN`` / ``query_vectors`` while the parameters stay unchanged."""
-    lib = _lib.load()
-    _require_gpu("core", core)
-    if core.dtype not in (torch.float32, torch.bfloat16):
-        raise RuntimeError(f"core must be float32 or bfloat16, got {core.dtype}")
-    bf16 = core.dtype == torch.bfloat16
-    core, R = _operand("core", core.detach(), core.dtype), _operand("R", R.detach(), core.dtype)
-    if core.dim() != 3 or R.dim() != 2 or R.shape[1] != core.shape[0]:
-        raise RuntimeError("expected core (a,b,c), R (nR,a)")
-    a, b, c = core.shape
-    if b != c:
-        raise RuntimeError(f"subject rank {b} must equal object rank {c} (asymmetric/R_TuckER.py:46)")
-    dev = core.device
-    n_rel = R.shape[0]
+    op = _Operands(core, R)
+    a, b, c, n_rel, dev = op.a, op.b, op.c, op.R.shape[0], op.dev
     tables = torch.empty((n_rel, b, c), dtype=torch.float32, device=dev)
-    dcode = _lib.RTK_BF16 if bf16 else _lib.RTK_F32
     with torch.cuda.device(dev):
-        sp = _stream_ptr(dev)
-        scratch = torch.empty(lib.rtk_relation_tables_workspace_bytes(dcode, n_rel, a, b, c), dtype=torch.uint8, device=dev)
-        fn = lib.rtk_relation_tables_bf16 if bf16 else lib.rtk_relation_tables_f32
-        _lib.check(fn(core.data_ptr(), a, b, c, R.data_ptr(), n_rel, tables.data_ptr(), scratch.data_ptr(), scratch.numel(), sp),
-                   "rtk_relation_tables")
+        scratch = torch.empty(_lib.load().rtk_relation_tables_workspace_bytes(op.dcode, n_rel, a, b, c), dtype=torch.uint8,
+                              device=dev)
+        _lib.check(_entry("rtk_relation_tables", op.bf16)(op.core.data_ptr(), a, b, c, op.R.data_ptr(), n_rel,
+                                                          tables.data_ptr(), scratch.data_ptr(), scratch.numel(),
+                                                          _stream_ptr(dev)), "rtk_relation_tables")
     return tables
 
 
 def _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v, sigmoid_mode=None, out=None,
              out_dtype=torch.float32, padded=None, tables=None):
-    lib = _lib.load()
-    _require_gpu("core", core)
-    if core.dtype not in (torch.float32, torch.bfloat16):
-        raise RuntimeError(f"core must be float32 or bfloat16, got {core.dtype}")
-    bf16 = core.dtype == torch.bfloat16
-    dt = core.dtype
-    core, R, S, O = _operand("core", core, dt), _operand("R", R, dt), _operand("S", S, dt), _operand("O", O, dt)
-    dev = core.device
-    for n, t in (("R", R), ("S", S), ("O", O)):
-        if t.device != dev:
-            raise RuntimeError(f"{n} is on {t.device}, core on {dev}")
-    if core.dim() != 3 or R.dim() != 2 or S.dim() != 2 or O.dim() != 2:
-        raise RuntimeError("expected core (a,b,c), R (nR,a), S (N,b), O (N,c)")
-    a, b, c = core.shape
-    if R.shape[1] != a or S.shape[1] != b or O.shape[1] != c:
-        raise RuntimeError(f"factor widths {R.shape[1]},{S.shape[1]},{O.shape[1]} do not match core {tuple(core.shape)}")
-    h = _idx("subject_idx", subject_idx, dev)
-    r = _idx("relation_idx", relation_idx, dev)
-    if h.numel() != r.numel():
-        raise RuntimeError(f"subject_idx has {h.numel()} entries, relation_idx {r.numel()}")
-    B, N = h.numel(), O.shape[0]
-    if b != c:
-        # asymmetric/R_TuckER.py:46: .view(-1, b) of a (B,1,c) tensor
-        raise RuntimeError(f"shape '[-1, {b}]' is invalid for input of size {B * c}")
-    if out_dtype not in (torch.float32, torch.bfloat16):
-        raise RuntimeError(f"out_dtype must be float32 or bfloat16, got {out_dtype}")
-    if out_dtype == torch.bfloat16 and (not bf16 or want_v or not sigmoid or exact):
+    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    flags = _score_flags(sigmoid, sigmoid_mode, out_dtype, op.bf16)
+    if out_dtype == torch.bfloat16 and (want_v or exact):
         raise RuntimeError("bfloat16 scores: bf16 operands, sigmoid=True, no autograd (the reference's bf16 eval path)")
+    B, N, dev = op.B, op.O.shape[0], op.dev
     if out is None:
         # dense when the scores are handed to autograd's caller, 128-byte aligned rows otherwise
         dense = want_v if padded is None else not padded
@@ -231,86 +316,35 @@ def _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v, s
     elif (tuple(out.shape) != (B, N) or out.dtype != out_dtype or out.device != dev or out.stride(1) != 1
           or out.stride(0) < N):
         raise RuntimeError(f"out must be a {out_dtype} ({B}, {N}) tensor on {dev} with unit column stride")
-    ld = out.stride(0) if B > 1 else N
     if B == 0:
-        return out, None
+        return out, None, op
+    packed = _packed_stage2(op.c, exact)
+    if op.bf16 and not packed:
+        raise RuntimeError(f"bf16 operands: only the bf16 MFMA score kernel exists (c <= {_PACKED_MAX_C}, exact=False)")
+    v = None
     with torch.cuda.device(dev):
         sp = _stream_ptr(dev)
-        dcode = _lib.RTK_BF16 if bf16 else _lib.RTK_F32
-        if tables is not None:
-            if (tables.dtype != torch.float32 or tables.device != dev or tuple(tables.shape) != (R.shape[0], b, c)
-                    or not tables.is_contiguous()):
-                raise RuntimeError(f"tables must be a contiguous float32 ({R.shape[0]}, {b}, {c}) tensor on {dev} "
-                                   "(ops.relation_tables)")
-            need = _size("rtk_from_tables_workspace_bytes", B, R.shape[0])
+        if tables is None and not want_v:
+            ws = op.workspace(sp)
+            _lib.check(_entry("rtk_score_1vN", op.bf16)(
+                op.core.data_ptr(), op.a, op.b, op.c, op.R.data_ptr(), op.R.shape[0], op.S.data_ptr(), op.S.shape[0],
+                op.O.data_ptr(), N, op.r.data_ptr(), op.h.data_ptr(), B, out.data_ptr(), out.stride(0) if B > 1 else N,
+                flags | (_lib.RTK_SCORE_EXACT_F32 if exact else 0), ws.data_ptr(), ws.numel(), sp), "rtk_score_1vN")
         else:
-            need = _size("rtk_workspace_bytes", dcode, B, R.shape[0], a, b, c)
-        ws = _workspace(dev, sp, need)
-        if bf16 and (exact or c > 512):
-            raise RuntimeError("bf16 operands: only the bf16 MFMA score kernel exists (c <= 512, exact=False)")
-        qv = lib.rtk_query_vectors_bf16 if bf16 else lib.rtk_query_vectors_f32
-        sp_fn = lib.rtk_score_packed_bf16 if bf16 else lib.rtk_score_packed_f32
-        s1vn = lib.rtk_score_1vN_bf16 if bf16 else lib.rtk_score_1vN_f32
-        mode = sigmoid_mode or DEFAULT_SIGMOID
-        if mode not in ("fast", "exact"):
-            raise ValueError(f"sigmoid mode must be 'fast' or 'exact', got {mode!r}")
-        flags = (_lib.RTK_SCORE_SIGMOID if sigmoid else 0) | (_lib.RTK_SCORE_EXACT_F32 if exact else 0)
-        flags |= _lib.RTK_SCORE_SIGMOID_FAST if (sigmoid and mode == "fast") else 0
-        if out_dtype == torch.bfloat16:
-            if mode != "fast":
-                raise RuntimeError("bfloat16 scores use the fast logistic (sigmoid_mode='fast')")
-            flags |= _lib.RTK_SCORE_OUT_BF16
-        sflags = flags & (_lib.RTK_SCORE_SIGMOID | _lib.RTK_SCORE_SIGMOID_FAST | _lib.RTK_SCORE_OUT_BF16)
-        v = None
-        if tables is not None:
-            # stage 1 against the prebuilt relation tables, then the score kernel on the packed planes
-            if exact or (not bf16 and c > 512):
-                v = torch.empty((B, c), dtype=torch.float32, device=dev)
-                qp = None
-            else:
-                v = torch.empty((B, c), dtype=torch.float32, device=dev) if want_v else None
-                qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", dcode, B, c))
-            ft = lib.rtk_query_vectors_from_tables_bf16 if bf16 else lib.rtk_query_vectors_from_tables_f32
-            _lib.check(ft(tables.data_ptr(), R.shape[0], b, c, S.data_ptr(), S.shape[0], r.data_ptr(), h.data_ptr(), B,
-                          v.data_ptr() if v is not None else None, qp.data_ptr() if qp is not None else None,
-                          ws.data_ptr(), ws.numel(), sp), "rtk_query_vectors_from_tables")
-            if qp is not None:
-                _lib.check(sp_fn(qp.data_ptr(), B, c, O.data_ptr(), N, out.data_ptr(), ld, sflags, sp), "rtk_score_packed")
-            else:
-                _lib.check(lib.rtk_score_f32(v.data_ptr(), B, c, O.data_ptr(), N, out.data_ptr(), ld,
-                                             flags & _lib.RTK_SCORE_SIGMOID, sp), "rtk_score_f32")
-        elif want_v:
-            # two-call form so the fp32 query vectors are kept for backward
-            v = torch.empty((B, c), dtype=torch.float32, device=dev)
-            use_packed = bf16 or (not exact and c <= 512)
-            qp = None
-            if use_packed:
-                qp = torch.empty(lib.rtk_packed_query_bytes(dcode, B, c), dtype=torch.uint8, device=dev)
-            _lib.check(qv(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0],
-                                                 S.data_ptr(), S.shape[0], r.data_ptr(), h.data_ptr(), B,
-                                                 v.data_ptr(), qp.data_ptr() if use_packed else None,
-                                                 ws.data_ptr(), ws.numel(), sp), "rtk_query_vectors")
-            if use_packed:
-                _lib.check(sp_fn(qp.data_ptr(), B, c, O.data_ptr(), N, out.data_ptr(), ld,
-                                 sflags & ~_lib.RTK_SCORE_OUT_BF16, sp), "rtk_score_packed_f32")
-            else:
-                _lib.check(lib.rtk_score_f32(v.data_ptr(), B, c, O.data_ptr(), N, out.data_ptr(), ld,
-                                             flags & _lib.RTK_SCORE_SIGMOID, sp), "rtk_score_f32")
-        else:
-            _lib.check(s1vn(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0],
-                                             S.data_ptr(), S.shape[0], O.data_ptr(), N,
-                                             r.data_ptr(), h.data_ptr(), B, out.data_ptr(), ld, flags,
-                                             ws.data_ptr(), ws.numel(), sp), "rtk_score_1vN_f32")
-        _strict_check(dev, ws, sp)
-    return out, v
+            # two calls: the fp32 query vectors are kept for backward, or stage 1 reads the relation tables
+            v = torch.empty((B, op.c), dtype=torch.float32, device=dev) if want_v or not packed else None
+            qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.c)) if packed else None
+            ws = _stage1(op, sp, tables, v, qp)
+            _stage2(op.bf16, sp, v, qp, op.O, out, flags)
+        _strict_check(ws, sp)
+    return out, v, op
 
 
 class _Score1vN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, core, R, S, O, subject_idx, relation_idx, sigmoid, exact, sigmoid_mode):
-        out, v = _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v=True, sigmoid_mode=sigmoid_mode)
-        dev = core.device
-        ctx.save_for_backward(core, R, S, O, _idx("s", subject_idx, dev), _idx("r", relation_idx, dev), v, out)
+        out, v, op = _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v=True, sigmoid_mode=sigmoid_mode)
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, out)
         ctx.sigmoid = sigmoid
         return out
 
@@ -468,12 +502,12 @@ class _BceLoss1vN(torch.autograd.Function):
     @staticmethod
     def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, label_smoothing):
         ctx.fused = False
-        if (FUSED_BCE and core.dtype == torch.float32 and core.is_cuda and core.shape[2] <= 512 and core.shape[1] == core.shape[2]
-                and subject_idx.numel() > 0):
+        if (FUSED_BCE and core.dtype == torch.float32 and core.is_cuda and _packed_stage2(core.shape[2], exact=False)
+                and core.shape[1] == core.shape[2] and subject_idx.numel() > 0):
             return _BceLoss1vN._forward_fused(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj,
                                               float(label_smoothing))
         # the scores never leave this function pair: aligned rows for them too
-        P, v = _forward(core, R, S, O, subject_idx, relation_idx, True, False, want_v=True, padded=True)
+        P, v, op = _forward(core, R, S, O, subject_idx, relation_idx, True, False, want_v=True, padded=True)
         lib = _lib.load()
         dev = P.device
         B, N = P.shape
@@ -482,8 +516,7 @@ class _BceLoss1vN(torch.autograd.Function):
             _lib.check(lib.rtk_bce_rows_f32(P.data_ptr(), B, N, P.stride(0), pair_slot.data_ptr(), pair_ptr.data_ptr(),
                                             pair_obj.data_ptr(), float(label_smoothing), rows.data_ptr(), _stream_ptr(dev)),
                        "rtk_bce_rows_f32")
-        ctx.save_for_backward(core, R, S, O, _idx("s", subject_idx, dev), _idx("r", relation_idx, dev), v, P,
-                              pair_slot, pair_ptr, pair_obj)
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, P, pair_slot, pair_ptr, pair_obj)
         ctx.eps = float(label_smoothing)
         return (rows.sum() / (B * N)).to(torch.float32)
 
@@ -493,23 +526,23 @@ class _BceLoss1vN(torch.autograd.Function):
         as ``x = p - eps / N`` (the logit gradient of a negative, up to g / (B N)), never re-read in the forward; the few
         positives are patched by ``rtk_bce_patch_pos_f32``."""
         lib = _lib.load()
-        dev = core.device
-        core, R, S, O = _f32c("core", core), _f32c("R", R), _f32c("S", S), _f32c("O", O)
-        h, r = _idx("subject_idx", subject_idx, dev), _idx("relation_idx", relation_idx, dev)
-        B, N, c = h.numel(), O.shape[0], core.shape[2]
-        v, qp = query_vectors(core.detach(), R.detach(), S.detach(), h, r, packed=True)
+        op = _Operands(core, R, S, O, subject_idx, relation_idx)
+        B, N, c, dev = op.B, op.O.shape[0], op.c, op.dev
+        v = torch.empty((B, c), dtype=torch.float32, device=dev)
         X = alloc_scores(B, N, dev)
         partials = torch.empty(lib.rtk_score_bce_partials(), dtype=torch.float64, device=dev)
         rows_pos = torch.empty(4 * B, dtype=torch.float64, device=dev)      # four partial sums per row
         ld = X.stride(0) if B > 1 else N
         with torch.cuda.device(dev):
             sp = _stream_ptr(dev)
-            _lib.check(lib.rtk_score_packed_bce_f32(qp.data_ptr(), B, c, O.data_ptr(), N, X.data_ptr(), ld, eps,
+            qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, c))
+            _strict_check(_stage1(op, sp, None, v, qp), sp)
+            _lib.check(lib.rtk_score_packed_bce_f32(qp.data_ptr(), B, c, op.O.data_ptr(), N, X.data_ptr(), ld, eps,
                                                     partials.data_ptr(), sp), "rtk_score_packed_bce_f32")
             _lib.check(lib.rtk_bce_patch_pos_f32(X.data_ptr(), B, N, ld, pair_slot.data_ptr(), pair_ptr.data_ptr(),
-                                                 pair_obj.data_ptr(), eps, v.data_ptr(), O.data_ptr(), c, rows_pos.data_ptr(), sp),
-                       "rtk_bce_patch_pos_f32")
-        ctx.save_for_backward(core, R, S, O, h, r, v, X, pair_slot, pair_ptr, pair_obj)
+                                                 pair_obj.data_ptr(), eps, v.data_ptr(), op.O.data_ptr(), c,
+                                                 rows_pos.data_ptr(), sp), "rtk_bce_patch_pos_f32")
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, X, pair_slot, pair_ptr, pair_obj)
         ctx.eps = eps
         ctx.fused = True
         return ((partials.sum() + rows_pos.sum()) / (B * N)).to(torch.float32)
@@ -576,9 +609,8 @@ def score_1vN(core, R, S, O, subject_idx, relation_idx, sigmoid=True, exact=Fals
         if out_dtype != torch.float32:
             raise RuntimeError("bfloat16 scores are an inference option (no autograd)")
         return _Score1vN.apply(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, sigmoid_mode)
-    out, _ = _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v=False, sigmoid_mode=sigmoid_mode,
-                      out_dtype=out_dtype, tables=tables)
-    return out
+    return _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v=False, sigmoid_mode=sigmoid_mode,
+                    out_dtype=out_dtype, tables=tables)[0]
 
 
 def score_1vN_into(core, R, S, O, subject_idx, relation_idx, out, sigmoid=True, exact=False, sigmoid_mode=None,
@@ -596,62 +628,34 @@ def query_vectors_part(core, R, S, subject_idx, relation_idx, tables, part, n_pa
     """Stage 1 for the queries whose relation id is congruent to ``part`` modulo ``n_parts`` only, against the prebuilt
     relation ``tables``: their rows of ``out`` (B, c) fp32 are written, the others left untouched
     (``rtk_query_vectors_from_tables_part_*``; the entity-sharded scorer's ``stage1="relation"``)."""
-    lib = _lib.load()
-    _require_gpu("core", core)
-    bf16 = core.dtype == torch.bfloat16
-    dt = core.dtype
-    core, R, S = _operand("core", core, dt), _operand("R", R, dt), _operand("S", S, dt)
-    dev = core.device
-    a, b, c = core.shape
-    h, r = _idx("subject_idx", subject_idx, dev), _idx("relation_idx", relation_idx, dev)
-    B = h.numel()
+    op = _Operands(core, R, S, None, subject_idx, relation_idx)
+    B, c, dev = op.B, op.c, op.dev
     if tuple(out.shape) != (B, c) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != dev:
         raise RuntimeError(f"out must be a contiguous float32 ({B}, {c}) tensor on {dev}")
-    if tables is None or tuple(tables.shape) != (R.shape[0], b, c) or tables.dtype != torch.float32 or not tables.is_contiguous():
-        raise RuntimeError("query_vectors_part needs the prebuilt relation tables (ops.relation_tables)")
+    op.check_tables(tables)
     if B == 0:
         return out
     with torch.cuda.device(dev):
         sp = _stream_ptr(dev)
-        ws = _workspace(dev, sp, _size("rtk_from_tables_workspace_bytes", B, R.shape[0]))
-        fn = lib.rtk_query_vectors_from_tables_part_bf16 if bf16 else lib.rtk_query_vectors_from_tables_part_f32
-        _lib.check(fn(tables.data_ptr(), R.shape[0], b, c, S.data_ptr(), S.shape[0], r.data_ptr(), h.data_ptr(), B,
-                      int(part), int(n_parts), out.data_ptr(), ws.data_ptr(), ws.numel(), sp),
-                   "rtk_query_vectors_from_tables_part")
-        _strict_check(dev, ws, sp)
+        ws = op.workspace(sp, tables)
+        _lib.check(_entry("rtk_query_vectors_from_tables_part", op.bf16)(
+            tables.data_ptr(), op.R.shape[0], op.b, c, op.S.data_ptr(), op.S.shape[0], op.r.data_ptr(), op.h.data_ptr(), B,
+            int(part), int(n_parts), out.data_ptr(), ws.data_ptr(), ws.numel(), sp), "rtk_query_vectors_from_tables_part")
+        _strict_check(ws, sp)
     return out
 
 
 def query_vectors(core, R, S, subject_idx, relation_idx, tables=None, packed=False):
     """Stage 1 only: ``v[d] = S[h_d] . (G x_0 R[r_d])`` -> ``(B, c)`` fp32 (R_TuckER.py:43-46).
     ``packed=True`` returns ``(v, q_packed)`` with the packed query planes the score kernels consume."""
-    lib = _lib.load()
-    _require_gpu("core", core)
-    bf16 = core.dtype == torch.bfloat16
-    dt = core.dtype
-    core, R, S = _operand("core", core, dt), _operand("R", R, dt), _operand("S", S, dt)
-    dev = core.device
-    a, b, c = core.shape
-    h, r = _idx("subject_idx", subject_idx, dev), _idx("relation_idx", relation_idx, dev)
-    B = h.numel()
-    dcode = _lib.RTK_BF16 if bf16 else _lib.RTK_F32
+    op = _Operands(core, R, S, None, subject_idx, relation_idx)
+    B, c, dev = op.B, op.c, op.dev
     v = torch.empty((B, c), dtype=torch.float32, device=dev)
-    qp = torch.empty(lib.rtk_packed_query_bytes(dcode, B, c), dtype=torch.uint8, device=dev) if packed else None
-    with torch.cuda.device(dev):
-        sp = _stream_ptr(dev)
-        if tables is not None:
-            ws = _workspace(dev, sp, lib.rtk_from_tables_workspace_bytes(B, R.shape[0]))
-            ft = lib.rtk_query_vectors_from_tables_bf16 if bf16 else lib.rtk_query_vectors_from_tables_f32
-            _lib.check(ft(tables.data_ptr(), R.shape[0], b, c, S.data_ptr(), S.shape[0], r.data_ptr(), h.data_ptr(), B,
-                          v.data_ptr(), qp.data_ptr() if packed else None, ws.data_ptr(), ws.numel(), sp),
-                       "rtk_query_vectors_from_tables")
-        else:
-            ws = _workspace(dev, sp, lib.rtk_workspace_bytes(dcode, B, R.shape[0], a, b, c))
-            qv = lib.rtk_query_vectors_bf16 if bf16 else lib.rtk_query_vectors_f32
-            _lib.check(qv(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0], S.data_ptr(),
-                          S.shape[0], r.data_ptr(), h.data_ptr(), B, v.data_ptr(), qp.data_ptr() if packed else None,
-                          ws.data_ptr(), ws.numel(), sp), "rtk_query_vectors")
-        _strict_check(dev, ws, sp)
+    qp = torch.empty(_size("rtk_packed_query_bytes", op.dcode, B, c), dtype=torch.uint8, device=dev) if packed else None
+    if B > 0:
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            _strict_check(_stage1(op, sp, tables, v, qp), sp)
     return (v, qp) if packed else v
 
 
@@ -660,15 +664,13 @@ def pack_query_vectors(v, dtype):
     operand type ``dtype`` -- the hand-over when stage 1 ran elsewhere (entity-sharded scoring with
     stage 1 split over the ranks: every rank contracts its slice of the batch, the B x c vectors are
     all-gathered, each rank packs them and scores its entity shard)."""
-    lib = _lib.load()
     _require_gpu("v", v)
     v = v.contiguous().float()
     B, c = v.shape
-    bf16 = dtype == torch.bfloat16
-    dcode = _lib.RTK_BF16 if bf16 else _lib.RTK_F32
-    qp = torch.empty(lib.rtk_packed_query_bytes(dcode, B, c), dtype=torch.uint8, device=v.device)
+    dcode = _dtype_code(dtype == torch.bfloat16)
+    qp = torch.empty(_size("rtk_packed_query_bytes", dcode, B, c), dtype=torch.uint8, device=v.device)
     with torch.cuda.device(v.device):
-        _lib.check(lib.rtk_pack_query_vectors(v.data_ptr(), B, c, dcode, qp.data_ptr(), _stream_ptr(v.device)),
+        _lib.check(_lib.load().rtk_pack_query_vectors(v.data_ptr(), B, c, dcode, qp.data_ptr(), _stream_ptr(v.device)),
                    "rtk_pack_query_vectors")
     return qp
 
@@ -676,24 +678,16 @@ def pack_query_vectors(v, dtype):
 def score_packed_into(qp, B, O, out, sigmoid=True, sigmoid_mode=None):
     """Stage 2 alone: ``out[d, j] = logistic(v_d . O[j])`` from packed query planes into a (B, n_local)
     buffer (float32, or bfloat16 for bf16 operands)."""
-    lib = _lib.load()
     _require_gpu("O", O)
     dev = O.device
     bf16 = O.dtype == torch.bfloat16
     O = O.contiguous()
-    N, c = O.shape
-    mode = sigmoid_mode or DEFAULT_SIGMOID
-    flags = (_lib.RTK_SCORE_SIGMOID if sigmoid else 0) | (_lib.RTK_SCORE_SIGMOID_FAST if (sigmoid and mode == "fast") else 0)
-    if out.dtype == torch.bfloat16:
-        if not bf16 or not sigmoid or mode != "fast":
-            raise RuntimeError("bfloat16 scores: bf16 operands and the fast logistic")
-        flags |= _lib.RTK_SCORE_OUT_BF16
+    N = O.shape[0]
+    flags = _score_flags(sigmoid, sigmoid_mode, out.dtype, bf16)
     if tuple(out.shape) != (B, N) or out.stride(1) != 1 or out.device != dev:
         raise RuntimeError(f"out must be ({B}, {N}) on {dev} with unit column stride")
-    fn = lib.rtk_score_packed_bf16 if bf16 else lib.rtk_score_packed_f32
     with torch.cuda.device(dev):
-        _lib.check(fn(qp.data_ptr(), B, c, O.data_ptr(), N, out.data_ptr(), out.stride(0) if B > 1 else N, flags,
-                      _stream_ptr(dev)), "rtk_score_packed")
+        _stage2(bf16, _stream_ptr(dev), None, qp, O, out, flags)
     return out
 
 

@@ -141,10 +141,8 @@ class ShardedEntityScorer:
 
     def _buffer(self, B, device, dtype):
         # rows start on 128-byte boundaries (ops.alloc_scores): the storage is (P, B, pitch)
-        from .ops import ROW_ALIGN
-        unit = ROW_ALIGN * (4 // torch.empty((), dtype=dtype).element_size()) if ROW_ALIGN > 1 else 1
-        pitch = -(-self.shards.n_loc // unit) * unit
-        need = (self.world, B, pitch)
+        from .ops import _row_pitch
+        need = (self.world, B, _row_pitch(self.shards.n_loc, dtype))
         g = self._gathered
         if g is None or tuple(g.shape) != need or g.device != device or g.dtype != dtype:
             g = torch.empty(need, dtype=dtype, device=device)

@@ -94,7 +94,7 @@ def test_sharded_rank_counts_sum_to_the_ranks(rt, shards):
 
 
 @pytest.mark.parametrize("variant", ["planted", "planted_sat", "spread"])
-def test_device_evaluate_wn18rr(rt, golden, golden_meta, variant):
+def test_device_evaluate_wn18rr(rt, golden, golden_meta, variant, monkeypatch):
     from r_tucker_amd.data import Data, KG_dataset
     data = Data(os.path.join(ROOT, "data", "WN18RR") + "/", reverse=True)
     n_ent, n_rel, rank, seed = len(data.entities), len(data.relations), (10, 200, 200), 322
@@ -129,3 +129,7 @@ def test_device_evaluate_wn18rr(rt, golden, golden_meta, variant):
     assert abs(bce.sum().item() / P.numel() - ref_bce) <= 2e-5 * max(1.0, abs(ref_bce))
     if variant != "planted_sat":      # massive exact ties at 1.0: the reference's own CPU tie order is arbitrary there
         assert abs(m["mrr"] - case["mrr"]) <= 1e-3
+    # an unknown logistic is rejected here as by the model closure
+    monkeypatch.setattr(rt.ops, "DEFAULT_SIGMOID", "bogus")
+    with pytest.raises(ValueError):
+        rt.evaluate(model, test, batch_size=512, flt=flt)

@@ -283,8 +283,29 @@ def test_within_row_dynamic_range(rt):
 def test_empty_batch_and_errors(rt):
     core, R, S, O = gen.make_params(50, 4, (3, 5, 5), 0)
     d = dev(core, R, S, O)
-    out = rt.score_1vN(*d, torch.zeros(0, dtype=torch.int64).cuda(), torch.zeros(0, dtype=torch.int64).cuda())
+    none = torch.zeros(0, dtype=torch.int64).cuda()
+    out = rt.score_1vN(*d, none, none)
     assert out.shape == (0, 50)
+    assert rt.query_vectors(*d[:3], none, none).shape == (0, 5)
+    with pytest.raises(ValueError):                    # an empty batch gets the same argument checks
+        rt.score_1vN(*d, none, none, sigmoid_mode="bogus")
+    # operands that do not fit the core are rejected before any kernel reads them (only WIDER ones here: a
+    # narrower one would be read out of bounds by a build without the check)
+    hq, rq = torch.tensor([0, 7]).cuda(), torch.tensor([1, 2]).cuda()
+    Rw, Sw = torch.cat([d[1], d[1][:, :1]], 1), torch.cat([d[2], d[2][:, :1]], 1)
+    tables = rt.relation_tables(*d[:2])
+    for bad in ((d[0], Rw, d[2]), (d[0], d[1], Sw)):
+        with pytest.raises(RuntimeError):
+            rt.query_vectors(*bad, hq, rq)
+    with pytest.raises(RuntimeError):
+        rt.query_vectors(*d[:3], hq, torch.tensor([1, 2, 3]).cuda())
+    with pytest.raises(RuntimeError):
+        rt.query_vectors(*d[:3], hq, rq, tables=torch.cat([tables, tables[:1]]))
+    with pytest.raises(RuntimeError):
+        rt.ops.query_vectors_part(d[0], d[1], Sw, hq, rq, tables, 0, 2, torch.zeros(2, 5).cuda())
+    _, qp = rt.query_vectors(*d[:3], hq, rq, packed=True)
+    with pytest.raises(ValueError):
+        rt.score_packed_into(qp, 2, d[3], rt.ops.alloc_scores(2, 50, d[3].device), sigmoid_mode="bogus")
     # b != c raises RuntimeError like the reference's view (golden meta: b_ne_c)
     core2, R2, S2, O2 = gen.make_params(20, 3, (3, 5, 7), 1)
     with pytest.raises(RuntimeError):
