@@ -226,7 +226,11 @@ int rtk_score_1vN_f32(const float *core, int a, int b, int c,
  * storage, torch.bfloat16), all accumulation is fp32, the query vectors are rounded to bf16
  * before the score product (v_mfma_f32_32x32x16_bf16), scores are fp32.  Same argument
  * meaning, workspace rules (query sizes with dtype = RTK_BF16) and reference lines as the
- * _f32 entry points above.
+ * _f32 entry points above.  rtk_score_packed_bf16 forms exact products and sums the c/16
+ * k-steps recursively in fp32: |z - v^.o| <= 2^-24 * 16 * ceil(c/16) * sum_k |v^_k||o_k| for the
+ * bf16-rounded v^.  The k-step order depends on c alone, not on n_local, batch, the
+ * logistic or the output type: a score has the same bits in every launch geometry (entity
+ * shards, query subsets, cached relation tables), and bf16 scores are the fp32 ones rounded.
  */
 int rtk_query_vectors_bf16(const void *core, int a, int b, int c,
                            const void *R, int64_t n_rel,

@@ -6,7 +6,7 @@
 // operand plane and no scaling: a wave keeps the bf16 B fragments of its 32 entity rows in
 // registers (loaded straight from O: a fragment IS 16 contiguous bytes of a row), the workgroup
 // sweeps 32-query tiles of the packed bf16 plane through a register-staged, double-buffered LDS
-// tile, KS MFMAs per tile on two alternating accumulators, logistic + branch-free buffer stores
+// tile, KS MFMAs per tile (two alternating accumulators at KS <= 16, one chain above), logistic + branch-free buffer stores
 // of the previous tile in the MFMA gaps.  With a third of the MFMA work of the fp32 path the
 // kernel is bound by the fp32 score write (HBM).
 #include "rtk_common.h"
@@ -305,7 +305,9 @@ __global__ __launch_bounds__(64 * NW, MINW) void score_bf16_kernel(
             for (int ks = 0; ks < KS; ++ks) {
                 const bf16x8 a = fa[ks % PF];
                 if (ks + PF < KS) fa[ks % PF] = la[(ks + PF) * 64 + lane];
-                if (ks & 1) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, Bf[ks], acc2, 0, 0, 0);
+                // KS > 16: one chain, the k-steps in the V2 loop's order -- both forms of a deep-K instantiation
+                // then give the same bits, whatever N and B pick (entity shards, cached tables)
+                if (KS <= 16 && (ks & 1)) acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, Bf[ks], acc2, 0, 0, 0);
                 else acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, Bf[ks], acc, 0, 0, 0);
                 if (STAGE_IN_CHAIN && ks < NLD && stage) stage_load_one(mt0 + i + 1, ks);
 #pragma unroll
@@ -313,7 +315,7 @@ __global__ __launch_bounds__(64 * NW, MINW) void score_bf16_kernel(
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
-            for (int e = 0; e < 16; ++e) prev[e] = acc[e] + acc2[e];
+            for (int e = 0; e < 16; ++e) prev[e] = KS <= 16 ? acc[e] + acc2[e] : acc[e];
             stage_store(cur ^ 1);   // unconditional: a stale tile in the spare buffer is never read
             __syncthreads();
         }
@@ -353,7 +355,9 @@ template <int KS, int SG, int MINW, int NW>
 int launch_one(const unsigned char *qp, int B, const rtk_bf16 *O, int N, int c, float *out, int64_t ld, bool o_vec,
                 bool obf, hipStream_t st) {
     const bool nts = (ld * (obf ? 2 : 4)) % 128 == 0 && (reinterpret_cast<uintptr_t>(out) & 127) == 0;
-    // deep-K form (NW == 8): the V2 loop, except for the exact logistic, which keeps round 2's two-chain loop
+    // deep-K form (NW == 8): the V2 loop, except for the exact logistic, which keeps the older loop.  At KS > 16 every
+    // loop sums the k-steps in one chain in the same order, so the 4- and 8-wave forms give the same bits: a score does
+    // not depend on N, B or the logistic mode (entity shards and cached tables are exact)
     constexpr bool V2 = NW == 8 && SG != 1;
     if constexpr (SG == 2) {   // bf16 scores: probabilities only (the caller checks)
         if (obf) {

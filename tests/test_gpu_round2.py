@@ -29,13 +29,17 @@ def dev(*xs):
 # ------------------------------------------------------------------ cached relation tables ----------
 @pytest.mark.parametrize("case", [
     # (n_ent, n_rel, B, rank, dtype)   small relation rank (VALU tables), planned batch (n_rel > B),
-    # large relation rank fp32 (GEMM tables), bf16 large rank (MFMA tables), grouped contract (B >= 2048)
+    # large relation rank fp32 (GEMM tables), bf16 large rank (MFMA tables), grouped contract (B >= 2048),
+    # bf16 relation rank > 256 (MFMA tables in both forms of the score kernel)
     (3000, 22, 96, (10, 200, 200), torch.float32),
     (1500, 300, 64, (6, 48, 48), torch.float32),
     (1200, 40, 80, (64, 64, 64), torch.float32),
     (2000, 37, 256, (96, 128, 128), torch.bfloat16),
     (900, 11, 2100, (8, 64, 64), torch.float32),
     (900, 50, 2048, (40, 64, 64), torch.bfloat16),
+    # bf16, a > 256 (KS = 19): the all-relations build (10 x 157 tiles of the score kernel) runs its 8-wave form,
+    # the per-batch build (64 slots: 2 x 157) its 4-wave form
+    (2000, 300, 64, (272, 200, 200), torch.bfloat16),
 ])
 def test_cached_tables_bit_identical_to_per_batch(rt, case):
     """rtk_relation_tables_* + rtk_query_vectors_from_tables_* give the bits of rtk_query_vectors_*: the
