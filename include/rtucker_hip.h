@@ -431,6 +431,41 @@ int rtk_filtered_rank_partial_f32(const float *P, int64_t batch, int64_t n_local
                                   int32_t *counts_out, double *bce_rows_out, void *stream);
 
 /*
+ * Filtered top-k link prediction: the k best objects of every (subject, relation, ?) row, leaving out the objects
+ * already known to be true -- what torch.topk on the score matrix cannot do (no exclusion list, no stable tie rule).
+ *   P          (batch x ld) scores, f32 or bf16 (bf16 values compare as bf16); read, never written
+ *   n_cols     candidates per row, ld >= n_cols
+ *   col0       column j of P is entity col0 + j (an entity block or shard of the full row) ...
+ *   col_ids    ... unless this (batch x ld_ids) int64 matrix is given ("merge mode", e.g. the concatenated top-k
+ *              lists of several shards or blocks): column j of row d is entity col_ids[d * ld_ids + j]; an id < 0
+ *              marks an absent candidate.  When a tie at the cut-off has to be split, merge mode takes the tied
+ *              candidates in column order: concatenated best-first lists of ascending id ranges have equal values
+ *              in ascending id order, so that is the id order
+ *   pair_slot  per row, index into the CSR of known-true objects (pair_ptr / pair_obj, as rtk_filtered_rank_f32),
+ *              or -1 for none; NULL: no filtering.  Those objects are REMOVED from the row (not set to 0 as
+ *              filter_predictions does); ids outside this block are ignored
+ *   keep_idx   optional, per row: an object never removed (-1 = none), e.g. the queried object
+ *   k          1 <= k <= 1024, else RTK_ERR_BAD_ARG
+ *   values_out (batch x k) float, ids_out (batch x k) int64: best first.  Descending by value; equal values by
+ *              ascending id (torch.sort(descending=True, stable=True) and rtk_filtered_rank_f32's order).  -0.0 and
+ *              +0.0 are equal (written as +0.0); every NaN ranks above +inf, NaNs tie with one another (written as
+ *              one quiet NaN).  A row with fewer than k eligible candidates is padded with (-inf, -1).
+ * Consistency with ranking: with keep_idx = obj_idx and a target score p_t > 0, rtk_filtered_rank_f32's rank r <= k
+ * iff ids_out[d, r - 1] == obj_idx[d]; for r > k the object is not in the row.
+ * One workgroup per row, deterministic; the workspace size is 0 at present (workspace may then be NULL).
+ * Arguments are validated before anything touches the device.
+ */
+size_t rtk_select_topk_workspace_bytes(int64_t batch, int64_t n_cols, int k);
+int rtk_select_topk_f32(const float *P, int64_t batch, int64_t n_cols, int64_t ld, int64_t col0,
+                        const int64_t *col_ids, int64_t ld_ids, const int64_t *pair_slot, const int64_t *pair_ptr,
+                        const int64_t *pair_obj, const int64_t *keep_idx, int k, float *values_out, int64_t *ids_out,
+                        void *workspace, size_t workspace_bytes, void *stream);
+int rtk_select_topk_bf16(const uint16_t *P, int64_t batch, int64_t n_cols, int64_t ld, int64_t col0,
+                         const int64_t *col_ids, int64_t ld_ids, const int64_t *pair_slot, const int64_t *pair_ptr,
+                         const int64_t *pair_obj, const int64_t *keep_idx, int k, float *values_out, int64_t *ids_out,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/*
  * Training loss without dense targets (train.py:76-82 with criterion = nn.BCELoss, train.py:136;
  * targets as src/data/Dataset.py:43-53 builds them: y = (1 - eps) * multi_hot + eps / N).
  * The multi-hot part is the CSR of known objects per (subject, relation) pair (pair_slot per row;

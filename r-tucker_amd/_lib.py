@@ -78,6 +78,9 @@ SIGNATURES = {
     "rtk_gram_factor_f64": (_i, [_p, _i64, _i, _i, C.c_double, C.c_double, _p, _p, _p]),
     "rtk_target_scores_f32": (_i, [_p, _i64, _i64, _i64, _i64, _p, _p, _p]),
     "rtk_filtered_rank_partial_f32": (_i, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "rtk_select_topk_workspace_bytes": (_sz, [_i64, _i64, _i]),
+    "rtk_select_topk_f32": (_i, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
+    "rtk_select_topk_bf16": (_i, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -52,12 +52,31 @@ class DeviceFilter:
             raise KeyError("an item's (subject, relation) pair is not among the dataset's pairs")
         slots = order[pos] if len(f) else np.zeros(0, np.int64)
         self.slot_of_item = torch.as_tensor(slots, device=self.device)
+        # the sorted pair keys, for slots_of (queries that are not dataset items)
+        self._pair_keys = torch.as_tensor(pk[order], device=self.device)
+        self._pair_order = torch.as_tensor(order.astype(np.int64), device=self.device)
+        self._key_nr = nr
         self.features = torch.as_tensor(f, device=self.device)
         # contiguous columns: the evaluation loop hands the kernels pointer offsets into them
         self.subj = self.features[:, 0].contiguous()
         self.rel = self.features[:, 1].contiguous()
         self.obj = self.features[:, 2].contiguous() if f.shape[1] > 2 else None
         self._plans = {}
+
+    def slots_of(self, subject_idx, relation_idx) -> torch.Tensor:
+        """CSR slot (int64, on the filter's device) of arbitrary (subject, relation) pairs, -1 for a pair the dataset
+        does not know: a binary search of the sorted pair keys, no host loop and no host sync."""
+        h = torch.as_tensor(subject_idx).to(device=self.device, dtype=torch.int64).reshape(-1)
+        r = torch.as_tensor(relation_idx).to(device=self.device, dtype=torch.int64).reshape(-1)
+        if h.numel() != r.numel():
+            raise RuntimeError(f"subject_idx has {h.numel()} entries, relation_idx {r.numel()}")
+        keys = self._pair_keys
+        if keys.numel() == 0:
+            return torch.full_like(h, -1)
+        q = h * self._key_nr + r
+        pos = torch.searchsorted(keys, q).clamp_(max=keys.numel() - 1)
+        hit = (keys[pos] == q) & (h >= 0) & (r >= 0) & (r < self._key_nr)
+        return torch.where(hit, self._pair_order[pos], torch.full_like(q, -1))
 
     @classmethod
     def of(cls, dataset, device):
@@ -97,6 +116,59 @@ def filtered_ranks(P: torch.Tensor, obj_idx: torch.Tensor, flt: DeviceFilter = N
                                              ranks.data_ptr(), bce.data_ptr() if want_bce else None, sp),
                    "rtk_filtered_rank_f32")
     return (ranks, bce) if want_bce else ranks
+
+
+def filtered_topk(P: torch.Tensor, k: int, flt: DeviceFilter = None, item_ids: torch.Tensor = None,
+                  keep_idx: torch.Tensor = None, slots: torch.Tensor = None, col0: int = 0, ids: torch.Tensor = None):
+    """The ``k`` best candidates of every row of ``P`` (float32 or bfloat16, (B, n), unit column stride), best first:
+    ``(values (B, k) float32, ids (B, k) int64)`` (``rtk_select_topk_*``).  Column j is entity ``col0 + j``, or, with
+    ``ids`` (a (B, n) int64 matrix, < 0 = absent), entity ``ids[d, j]`` (merging top-k lists).
+
+    Order of ``torch.sort(descending=True, stable=True)``: equal scores by ascending id; -0.0 == +0.0; NaN above +inf.
+    Filtering (``flt``, a ``DeviceFilter``): the row's known-true objects are REMOVED (not set to 0), except
+    ``keep_idx[d]`` (-1 = none).  The filter row comes from ``item_ids`` (dataset items) or from ``slots``
+    (``flt.slots_of(subject_idx, relation_idx)``; -1 = no filtering).  A row with fewer than k eligible candidates
+    is padded with (-inf, -1).  ``P`` is not modified."""
+    lib = _lib.load()
+    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dim() != 2 or P.dtype not in (torch.float32, torch.bfloat16)
+            or (P.shape[1] > 1 and P.stride(1) != 1)):
+        raise RuntimeError("P must be a float32 or bfloat16 (B, n) GPU tensor with unit column stride")
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError(f"k = {k}: the selection takes 1 <= k <= 1024")
+    B, n = P.shape
+    dev = P.device
+
+    def per_row(name, t):
+        t = torch.as_tensor(t).to(device=dev, dtype=torch.int64).contiguous().view(-1)
+        if t.numel() != B:
+            raise RuntimeError(f"{name} must have one entry per row of P")
+        return t
+    slot = None
+    if flt is not None:
+        if slots is None and item_ids is None:
+            raise ValueError("filtering needs the rows' filter slots: item_ids (dataset items) or slots (flt.slots_of)")
+        slot = per_row("slots", slots if slots is not None else flt.slot_of_item[torch.as_tensor(item_ids).to(dev)])
+    elif slots is not None or item_ids is not None:
+        raise ValueError("slots / item_ids need flt (the DeviceFilter that holds the CSR)")
+    keep = per_row("keep_idx", keep_idx) if keep_idx is not None else None
+    if ids is not None:
+        if (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.device != dev
+                or tuple(ids.shape) != (B, n) or (n > 1 and ids.stride(1) != 1)):
+            raise RuntimeError(f"ids must be an int64 ({B}, {n}) tensor on {dev} with unit column stride")
+    values = torch.empty((B, k), dtype=torch.float32, device=dev)
+    out_ids = torch.empty((B, k), dtype=torch.int64, device=dev)
+    ld = P.stride(0) if B > 1 else n
+    ld_ids = (ids.stride(0) if B > 1 else n) if ids is not None else 0
+    fn = lib.rtk_select_topk_bf16 if P.dtype == torch.bfloat16 else lib.rtk_select_topk_f32
+    with torch.cuda.device(dev):
+        _lib.check(fn(P.data_ptr(), B, n, ld, int(col0), ids.data_ptr() if ids is not None else None, ld_ids,
+                      slot.data_ptr() if slot is not None else None,
+                      flt.pair_ptr.data_ptr() if slot is not None else None,
+                      flt.pair_obj.data_ptr() if slot is not None else None,
+                      keep.data_ptr() if keep is not None else None, k, values.data_ptr(), out_ids.data_ptr(), None, 0,
+                      torch.cuda.current_stream(dev).cuda_stream), "rtk_select_topk")
+    return values, out_ids
 
 
 def target_scores_block(P: torch.Tensor, obj_idx: torch.Tensor, col0: int) -> torch.Tensor:

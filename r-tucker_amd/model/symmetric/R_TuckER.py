@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from ...ops import score_1vN
+from ...ops import score_1vN, topk_1vN
 from .._tables import TablesCacheMixin
 
 
@@ -43,3 +43,13 @@ class R_TuckER(TablesCacheMixin, nn.Module):
             return score_1vN(T.core, T.regular_factors[0], E, E, subject_idx, relation_idx, tables=tables)
 
         return score_fn
+
+    @torch.no_grad()
+    def predict(self, subject_idx, relation_idx, k=10, flt=None, **kw):
+        """The ``k`` most likely objects of each ``(subject, relation, ?)`` query, best first: ``(values, ids)``
+        (``ops.topk_1vN``; ``flt``: a ``DeviceFilter`` whose known-true objects are left out).  In eval mode the
+        relation tables are built once and reused, as by the scoring closure."""
+        tables = kw.pop("tables", None)
+        if tables is None:
+            tables = self._cached_tables(self.core, self.R.weight)
+        return topk_1vN(self.core, self.R.weight, self.E.weight, self.E.weight, subject_idx, relation_idx, k, flt=flt, tables=tables, **kw)

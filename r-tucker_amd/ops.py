@@ -691,6 +691,70 @@ def score_packed_into(qp, B, O, out, sigmoid=True, sigmoid_mode=None):
     return out
 
 
+_topk_scores = {}   # (device index, stream, dtype) -> score buffer of topk_1vN, reused by every call on that stream
+
+
+def _topk_score_buffer(device, stream_ptr, B, N, dtype):
+    """(B, N) view, rows on 128-byte boundaries, of the per-stream buffer topk_1vN scores into: its scores are consumed
+    by the select on the same stream before the next call overwrites them."""
+    key = (device.index, stream_ptr, dtype)
+    pitch = _row_pitch(N, dtype)
+    buf = _topk_scores.get(key)
+    if buf is None or buf.numel() < B * pitch:
+        buf = _topk_scores[key] = torch.empty(max(B * pitch, 1), dtype=dtype, device=device)
+    return buf[:B * pitch].view(B, pitch)[:, :N]
+
+
+@torch.no_grad()
+def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=None, sigmoid=True, sigmoid_mode=None,
+             score_dtype=torch.float32, tables=None, entity_block=None):
+    """Filtered top-k link prediction: the ``k`` most likely objects of every ``(h, r, ?)`` query, best first, as
+    ``(values (B, k) float32, ids (B, k) int64)`` -- the filtered, stable descending sort of ``score_1vN``'s rows cut
+    at k, without sorting them (``evaluation.filtered_topk``).  ``flt`` (a ``DeviceFilter``): the known-true objects
+    of each query's pair (``flt.slots_of``) are left out, except ``keep_idx[d]``.  Rows with fewer than k candidates
+    are padded with (-inf, -1).  Inference only (no autograd).
+
+    Default: stage 1 once, stage 2 into a per-stream buffer reused across calls, then the select; the scores are
+    bit-identical to ``score_1vN`` with the same arguments (``score_dtype``: its ``out_dtype``), so the result is exactly
+    the filtered stable sort of ``score_1vN``'s output.
+    ``entity_block=n``: the entities are scored ``n`` at a time into a (B, n) buffer (``score_packed_into`` on the packed
+    query vectors), each block's top k is selected and merged into the running top k -- memory B x n instead of B x N.
+    Block scores may differ from full-width scores in the last bits (the fp32 kernel's fifth column group depends on
+    the column count, ``cg_fifth_group_columns``); the result is exact for the scores as computed."""
+    from .evaluation import filtered_topk
+    k = int(k)
+    if not 1 <= k <= 1024:
+        raise ValueError(f"k = {k}: the selection takes 1 <= k <= 1024")
+    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    B, N, dev = op.B, op.O.shape[0], op.dev
+    slots = flt.slots_of(op.h, op.r) if flt is not None else None
+    if entity_block is None:
+        with torch.cuda.device(dev):
+            out = _topk_score_buffer(dev, _stream_ptr(dev), B, N, score_dtype)
+        _forward(core, R, S, O, op.h, op.r, sigmoid, False, want_v=False, sigmoid_mode=sigmoid_mode, out=out,
+                 out_dtype=score_dtype, tables=tables)
+        return filtered_topk(out, k, flt, keep_idx=keep_idx, slots=slots)
+    n = int(entity_block)
+    if n <= 0:
+        raise ValueError(f"entity_block must be positive, got {entity_block}")
+    if not _packed_stage2(op.c, exact=False):
+        raise RuntimeError(f"entity_block needs the packed score kernels (object rank c <= {_PACKED_MAX_C})")
+    _score_flags(sigmoid, sigmoid_mode, score_dtype, op.bf16)          # (the score buffer's dtype is valid)
+    _, qp = query_vectors(core, R, S, op.h, op.r, tables=tables, packed=True)
+    with torch.cuda.device(dev):
+        buf = _topk_score_buffer(dev, _stream_ptr(dev), B, min(n, max(N, 1)), score_dtype)
+    values = torch.full((B, k), float("-inf"), dtype=torch.float32, device=dev)
+    ids = torch.full((B, k), -1, dtype=torch.int64, device=dev)
+    for lo in range(0, N, n):
+        nb = min(n, N - lo)
+        blk = buf[:, :nb]
+        score_packed_into(qp, B, op.O[lo:lo + nb], blk, sigmoid=sigmoid, sigmoid_mode=sigmoid_mode)
+        bv, bi = filtered_topk(blk, k, flt, keep_idx=keep_idx, slots=slots, col0=lo)
+        # running list first: its ids are all below lo, so tied values stay in ascending id order
+        values, ids = (bv, bi) if lo == 0 else filtered_topk(torch.cat([values, bv], 1), k, ids=torch.cat([ids, bi], 1))
+    return values, ids
+
+
 def cg_fifth_group_columns(N, c, flags=0):
     """Boolean mask (N,) of the entity columns that the default fp32 score kernel computes as FOUR K-range chains added
     in a fixed order instead of one chain -- the fifth column group of a workgroup's set in the column-group kernel

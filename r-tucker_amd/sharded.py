@@ -267,3 +267,37 @@ class ShardedEntityScorer:
                 dist.all_reduce(bce, op=dist.ReduceOp.SUM, group=self.group)
         ranks = counts + 1
         return (ranks, bce) if want_bce else ranks
+
+    # ---- top-k without the gather ----------------------------------------------------------
+    def topk(self, core, R, S, O_loc, subject_idx, relation_idx, k, flt=None, slots=None, keep_idx=None,
+             local_topk_fn=None, merge_fn=None, **kw):
+        """Filtered top-k objects (``(values, ids)``, (B, k), global entity ids, best first) with the entity matrix
+        row-sharded and NO exchange of scores: each rank scores its block and selects its top k over its real
+        columns (``col0 = rank * n_loc``; the last shard's padding rows are never candidates), the (B, k) lists are
+        all-gathered -- B k 12 bytes per rank instead of B N 4 -- and merged.  Same result as ``filtered_topk`` on the
+        gathered matrix.  ``slots`` default to ``flt.slots_of(subject_idx, relation_idx)``.
+
+        ``local_topk_fn(P_block, k, col0, flt, slots, keep_idx)`` / ``merge_fn(values, ids, k)`` default to the HIP
+        select (``evaluation.filtered_topk``, plain and merge mode); tests inject CPU functions."""
+        if local_topk_fn is None or merge_fn is None:
+            from .evaluation import filtered_topk
+            local_topk_fn = local_topk_fn or (lambda P, k_, col0, flt_, slots_, keep_: filtered_topk(
+                P, k_, flt_, keep_idx=keep_, slots=slots_, col0=col0))
+            merge_fn = merge_fn or (lambda v, i, k_: filtered_topk(v, k_, ids=i))
+        B = int(subject_idx.numel())
+        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
+        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))
+        if slots is None and flt is not None:
+            slots = flt.slots_of(subject_idx, relation_idx)
+        g = self._buffer(B, core.device, self.score_dtype)
+        mine = g[self.rank][:, :n_loc]
+        self._score_local(core, R, S, O_loc, subject_idx, relation_idx, mine, **kw)
+        values, ids = local_topk_fn(mine[:, :n_valid], k, lo, flt, slots, keep_idx)
+        if self.world == 1:
+            return values, ids
+        gv = torch.empty((self.world, B, k), dtype=values.dtype, device=values.device)
+        gi = torch.empty((self.world, B, k), dtype=ids.dtype, device=ids.device)
+        dist.all_gather_into_tensor(gv.view(-1), values.contiguous().view(-1), group=self.group)
+        dist.all_gather_into_tensor(gi.view(-1), ids.contiguous().view(-1), group=self.group)
+        # rank order = ascending id ranges: tied values stay in ascending id order for the merge
+        return merge_fn(gv.permute(1, 0, 2).reshape(B, self.world * k), gi.permute(1, 0, 2).reshape(B, self.world * k), k)
