@@ -104,7 +104,8 @@ const char *rtk_last_error_string(void);
 size_t rtk_workspace_bytes(int dtype, int64_t batch, int64_t n_rel, int a, int b, int c);
 
 /* Fetches and clears the device error word of a workspace (hipStreamSynchronize
- * on `stream` first).  Bit 0: relation/subject index out of range. */
+ * on `stream` first).  Bit 0: relation/subject index out of range.  Bit 1: a
+ * candidate id of rtk_score_candidates_* out of range. */
 int rtk_read_error_flag(void *workspace, void *stream, uint32_t *host_flag_out);
 
 /*
@@ -464,6 +465,58 @@ int rtk_select_topk_bf16(const uint16_t *P, int64_t batch, int64_t n_cols, int64
                          const int64_t *col_ids, int64_t ld_ids, const int64_t *pair_slot, const int64_t *pair_ptr,
                          const int64_t *pair_obj, const int64_t *keep_idx, int k, float *values_out, int64_t *ids_out,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Candidate scoring: each query scores its own list of K entities instead of all N (triple scoring: K = 1;
+ * sampled negatives; candidate-set evaluation).
+ *   z[d, k] = v[d, :] . O[cand[d * ld_cand + k], :]        out[d * ld_out + k] = z, or its logistic
+ *   v     (batch x c) fp32 query vectors (stage 1: rtk_query_vectors_*, or their v_out); c in [1, 1024]
+ *   O     (n_ent x c) fp32 (_f32) or bf16 (_bf16, read as bf16); any c, any 4-byte-aligned O
+ *   cand  int64, row d at cand + d * ld_cand; ld_cand == 0: one list of K ids shared by every query
+ *   out   fp32 (batch x ld_out), ld_out >= K
+ *   flags RTK_SCORE_SIGMOID, RTK_SCORE_SIGMOID_FAST with the meaning they have for rtk_score_packed_*
+ *   workspace  the error word's holder: a 256-byte-aligned buffer of >= 256 bytes whose first word is the error
+ *              word (the workspace of the stage 1 that made v serves)
+ * Arithmetic: _bf16 rounds v to bf16 (v^) first, as rtk_score_packed_bf16; products are formed by fmaf (exact for
+ * bf16 x bf16).  A wave holds the row: lane l takes the m elements j = i * W + l * w + q (w = 4 fp32 / 8 bf16,
+ * W = 64 w, m = w * ceil(c / W)), sums them by an fmaf chain in (i, q) order, and the 64 lane sums are added by a
+ * 6-level xor butterfly.  So  |z - v.o| <= gamma(m + 6) * sum_j |v_j||o_j|,  gamma(n) = n 2^-24 / (1 - n 2^-24)
+ * (for _bf16 with v^ in place of v); m + 6 <= 22.
+ * Determinism: that order depends on c alone.  The bits of z[d, k] depend only on v[d], O[e] and c -- not on k, K,
+ * batch, ld_cand, ld_out, n_ent, or the other candidates of the wave: a triple scores the same in every list.
+ * An id outside [0, n_ent) is clamped for the load, its entry is written as NaN and bit 1 of the error word is set.
+ * Refused with RTK_ERR_BAD_ARG before anything is enqueued: null pointers, c < 1, batch < 0, K < 0, n_ent < 1,
+ * ld_cand neither 0 nor >= K, ld_out < K, flags other than the two above, a workspace under 256 bytes or not
+ * 256-byte aligned.  c > 1024 or batch x K >= 2^31: RTK_ERR_UNSUPPORTED.
+ */
+int rtk_score_candidates_f32(const float *v, int64_t batch, int c, const float *O, int64_t n_ent,
+                             const int64_t *cand, int64_t ld_cand, int64_t k, float *out, int64_t ld_out,
+                             unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
+int rtk_score_candidates_bf16(const float *v, int64_t batch, int c, const void *O, int64_t n_ent,
+                              const int64_t *cand, int64_t ld_cand, int64_t k, float *out, int64_t ld_out,
+                              unsigned flags, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Backward of the candidate scores (of the logits z: apply the logistic's derivative first), dZ (batch x ld_dz):
+ *   dv[d, :]  = sum_k dZ[d, k] O[cand[d, k], :]                 fp32 (batch x c); O read as fp32 or bf16
+ *   gO[e, :]  = sum_{(d, k): cand[d, k] = e} dZ[d, k] v[d, :]    fp32 (n_ent x c), written in full (rows no
+ *               candidate names are 0); v is the fp32 query vector (for _bf16 not rounded: the rule of the 1-vs-N
+ *               backward)
+ * Either output may be NULL.  Out-of-range candidates add nothing to either.  No float atomics; two runs give the
+ * same bits:  dv sums each quarter of a row's list in increasing k and adds the quarters in order;  gO orders the
+ * entries d K + k by entity on the device (stable radix sort: counts, offsets, a stable fill), sums each entity's
+ * list in increasing d K + k in chunks (batch K / 4096 entries rounded up to 16, clamped to [16, 256]: a function of
+ * batch K alone), and adds the chunk sums in chunk order.
+ * The workspace (rtk_score_candidates_bwd_workspace_bytes, 256-byte aligned) is needed when gO is given.
+ * Argument rules as the forward, and ld_dz >= K.
+ */
+size_t rtk_score_candidates_bwd_workspace_bytes(int64_t batch, int64_t k, int64_t n_ent);
+int rtk_score_candidates_bwd_f32(const float *dz, int64_t ld_dz, const float *v, int64_t batch, int c,
+                                 const float *O, int64_t n_ent, const int64_t *cand, int64_t ld_cand, int64_t k,
+                                 float *dv, float *gO, void *workspace, size_t workspace_bytes, void *stream);
+int rtk_score_candidates_bwd_bf16(const float *dz, int64_t ld_dz, const float *v, int64_t batch, int c,
+                                  const void *O, int64_t n_ent, const int64_t *cand, int64_t ld_cand, int64_t k,
+                                  float *dv, float *gO, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Training loss without dense targets (train.py:76-82 with criterion = nn.BCELoss, train.py:136;

@@ -81,6 +81,11 @@ SIGNATURES = {
     "rtk_select_topk_workspace_bytes": (_sz, [_i64, _i64, _i]),
     "rtk_select_topk_f32": (_i, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
     "rtk_select_topk_bf16": (_i, [_p, _i64, _i64, _i64, _i64, _p, _i64, _p, _p, _p, _p, _i, _p, _p, _p, _sz, _p]),
+    "rtk_score_candidates_f32": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _i64, _p, _i64, _u, _p, _sz, _p]),
+    "rtk_score_candidates_bf16": (_i, [_p, _i64, _i, _p, _i64, _p, _i64, _i64, _p, _i64, _u, _p, _sz, _p]),
+    "rtk_score_candidates_bwd_workspace_bytes": (_sz, [_i64, _i64, _i64]),
+    "rtk_score_candidates_bwd_f32": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
+    "rtk_score_candidates_bwd_bf16": (_i, [_p, _i64, _p, _i64, _i, _p, _i64, _p, _i64, _i64, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -277,7 +277,7 @@ extern "C" int rtk_timer_destroy(void *timer) {
     return RTK_OK;
 }
 
-extern "C" int rtk_version(void) { return 213; }
+extern "C" int rtk_version(void) { return 214; }
 extern "C" const char *rtk_last_error_string(void) { return g_err; }
 
 extern "C" size_t rtk_workspace_bytes(int dtype, int64_t batch, int64_t n_rel, int a, int b, int c) {

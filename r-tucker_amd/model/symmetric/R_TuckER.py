@@ -10,7 +10,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from ...ops import score_1vN, topk_1vN
+from ...ops import score_1vN, score_candidates, score_triples, topk_1vN
 from .._tables import TablesCacheMixin
 
 
@@ -41,6 +41,26 @@ class R_TuckER(TablesCacheMixin, nn.Module):
             E = T.shared_factor
             tables = self._cached_tables(T.core, T.regular_factors[0])
             return score_1vN(T.core, T.regular_factors[0], E, E, subject_idx, relation_idx, tables=tables)
+
+        return score_fn
+
+    def score_candidates(self, subject_idx, relation_idx, candidates):
+        """``score_fn(T)`` giving the (B, K) scores of each query against its own candidate entities
+        (``ops.score_candidates``; ``candidates`` int64 (B, K) on the device).  Like ``forward``, the sizes come from
+        T, so it serves the doubled-rank T of training; in eval mode the relation tables are cached.  ``E`` is passed as both S and O; autograd sums the two gradients."""
+        def score_fn(T):
+            E = T.shared_factor
+            tables = self._cached_tables(T.core, T.regular_factors[0])
+            return score_candidates(T.core, T.regular_factors[0], E, E, subject_idx, relation_idx, candidates, tables=tables)
+
+        return score_fn
+
+    def score_triples(self, subject_idx, relation_idx, object_idx):
+        """``score_fn(T)`` giving the (B,) scores of the triples (h, r, t) (``ops.score_triples``)."""
+        def score_fn(T):
+            E = T.shared_factor
+            tables = self._cached_tables(T.core, T.regular_factors[0])
+            return score_triples(T.core, T.regular_factors[0], E, E, subject_idx, relation_idx, object_idx, tables=tables)
 
         return score_fn
 

@@ -218,6 +218,8 @@ def _check_now(ws, sp):
     _lib.check(_lib.load().rtk_read_error_flag(ws.data_ptr(), sp, C.byref(flag)), "rtk_read_error_flag")
     if flag.value & 1:
         raise IndexError("index out of range in self (subject_idx / relation_idx)")
+    if flag.value & 2:
+        raise IndexError("index out of range in self (candidate id out of range)")
 
 
 def _strict_check(ws, sp):
@@ -753,6 +755,147 @@ def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=Non
         # running list first: its ids are all below lo, so tied values stay in ascending id order
         values, ids = (bv, bi) if lo == 0 else filtered_topk(torch.cat([values, bv], 1), k, ids=torch.cat([ids, bi], 1))
     return values, ids
+
+
+def _candidates(name, t, B, dev):
+    """``(tensor, ld_cand, K)`` of a (B, K) int64 candidate matrix on ``dev`` with unit column stride; a row broadcast
+    over the batch (``cand.expand(B, K)``, row stride 0) is one shared list (``ld_cand = 0``)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64 or t.dim() != 2:
+        raise RuntimeError(f"{name} must be an int64 (B, K) tensor, got "
+                           + (f"{t.dtype} {tuple(t.shape)}" if isinstance(t, torch.Tensor) else str(type(t))))
+    _require_gpu(name, t)
+    if t.device != dev:
+        raise RuntimeError(f"{name} is on {t.device}, the operands on {dev}")
+    if t.shape[0] != B:
+        raise RuntimeError(f"{name} has {t.shape[0]} rows for {B} queries")
+    K = t.shape[1]
+    if K > 1 and t.stride(1) != 1:
+        raise RuntimeError(f"{name} must have unit column stride")
+    ld = t.stride(0) if B > 1 else K
+    if ld != 0 and ld < K:
+        raise RuntimeError(f"{name}: row stride {ld} below K = {K} (rows must not overlap)")
+    return t, ld, K
+
+
+def _candidate_forward(op, cand, ld, K, flags, tables, want_v):
+    """Stage 1 into fp32 query vectors, then ``rtk_score_candidates_*`` -> (B, K) fp32 scores, and v when asked."""
+    B, dev = op.B, op.dev
+    out = torch.empty((B, K), dtype=torch.float32, device=dev)
+    if B == 0 or K == 0:
+        return out, (torch.empty((B, op.c), dtype=torch.float32, device=dev) if want_v else None)
+    v = torch.empty((B, op.c), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        sp = _stream_ptr(dev)
+        ws = _stage1(op, sp, tables, v, None)
+        _lib.check(_entry("rtk_score_candidates", op.bf16)(
+            v.data_ptr(), B, op.c, op.O.data_ptr(), op.O.shape[0], cand.data_ptr(), ld, K, out.data_ptr(), K, flags,
+            ws.data_ptr(), ws.numel(), sp), "rtk_score_candidates")
+        _strict_check(ws, sp)
+    return out, (v if want_v else None)
+
+
+def _stage1_backward(core, R, S, h, r, dv, needs):
+    """(g_core, g_R, g_S) fp32 from dv through ``rtk_query_vectors_bwd_f32``."""
+    lib = _lib.load()
+    dev = dv.device
+    a, b, c = core.shape
+    B = dv.shape[0]
+    gcore = torch.empty_like(core) if needs[0] else None
+    gR = torch.empty_like(R) if needs[1] else None
+    gS = torch.empty_like(S) if needs[2] else None
+    with torch.cuda.device(dev):
+        bws = torch.empty(lib.rtk_query_bwd_workspace_bytes(B, a, b, c), dtype=torch.uint8, device=dev)
+        _lib.check(lib.rtk_query_vectors_bwd_f32(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0], S.data_ptr(),
+                                                 S.shape[0], r.data_ptr(), h.data_ptr(), B, dv.data_ptr(),
+                                                 gcore.data_ptr() if needs[0] else None,
+                                                 gR.data_ptr() if needs[1] else None,
+                                                 gS.data_ptr() if needs[2] else None,
+                                                 bws.data_ptr(), bws.numel(), _stream_ptr(dev)), "rtk_query_vectors_bwd_f32")
+    return gcore, gR, gS
+
+
+class _ScoreCandidates(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, core, R, S, O, subject_idx, relation_idx, candidates, sigmoid, sigmoid_mode):
+        op = _Operands(core, R, S, O, subject_idx, relation_idx)
+        cand, ld, K = _candidates("candidates", candidates, op.B, op.dev)
+        flags = _score_flags(sigmoid, sigmoid_mode, torch.float32, op.bf16)
+        out, v = _candidate_forward(op, cand, ld, K, flags, None, want_v=True)
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, cand, v, out)
+        ctx.sigmoid, ctx.ld = sigmoid, ld
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        core, R, S, O, h, r, cand, v, out = ctx.saved_tensors
+        needs = ctx.needs_input_grad
+        pdt = core.dtype                      # bf16 operands: gradients computed in fp32, returned in bf16
+        B, K = out.shape
+        N, c = O.shape
+        dev = out.device
+        g = [None] * 4
+        if B == 0 or K == 0:
+            g = [torch.zeros_like(t) if n else None for t, n in zip((core, R, S, O), needs[:4])]
+            return tuple(g) + (None,) * 5
+        lib = _lib.load()
+        bf16 = pdt == torch.bfloat16
+        grad_out = grad_out.contiguous().float()
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            if ctx.sigmoid:                   # dZ = dP * P * (1 - P); the NaN entries of bad ids are skipped below
+                dZ = torch.empty_like(out)
+                _lib.check(lib.rtk_sigmoid_grad_f32(grad_out.data_ptr(), out.data_ptr(), dZ.data_ptr(), out.numel(), sp),
+                           "rtk_sigmoid_grad_f32")
+            else:
+                dZ = grad_out
+            want_dv = needs[0] or needs[1] or needs[2]
+            dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
+            gO = torch.empty((N, c), dtype=torch.float32, device=dev) if needs[3] else None
+            nws = lib.rtk_score_candidates_bwd_workspace_bytes(B, K, N) if needs[3] else 0
+            ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=dev)
+            _lib.check(_entry("rtk_score_candidates_bwd", bf16)(
+                dZ.data_ptr(), K, v.data_ptr(), B, c, O.data_ptr(), N, cand.data_ptr(), ctx.ld, K,
+                dv.data_ptr() if want_dv else None, gO.data_ptr() if needs[3] else None, ws.data_ptr(), ws.numel(), sp),
+                "rtk_score_candidates_bwd")
+        if want_dv:
+            if bf16:
+                core, R, S = core.float(), R.float(), S.float()
+            g[0], g[1], g[2] = _stage1_backward(core, R, S, h, r, dv, needs)
+        g[3] = gO
+        if bf16:
+            g = [x.to(pdt) if x is not None else None for x in g]
+        # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
+        return tuple(g) + (None,) * 5
+
+
+def score_candidates(core, R, S, O, subject_idx, relation_idx, candidates, sigmoid=True, sigmoid_mode=None,
+                     tables=None):
+    """``sigmoid(v_d . O[candidates[d, k]])`` -> ``(B, K)`` fp32: each query scored against its own list of K entities
+    (``rtk_score_candidates_*``) instead of all N.  ``candidates``: int64 (B, K) on the operands' device, unit column
+    stride; ``cand.expand(B, K)`` of one row is a list shared by every query.  A score depends only on the query, the
+    entity and c: the same triple has the same bits in every list, at every K and batch split.  Differentiable with
+    respect to core, R, S and O (bf16 operands: gradients computed in fp32, returned in bf16).  ``tables`` (no
+    autograd): prebuilt relation tables, as for ``score_1vN``.  An id outside [0, N) gives a NaN entry and raises
+    ``IndexError`` by the ``index_check`` policy."""
+    needs_grad = torch.is_grad_enabled() and any(
+        isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S, O))
+    if needs_grad:
+        return _ScoreCandidates.apply(core, R, S, O, subject_idx, relation_idx, candidates, sigmoid, sigmoid_mode)
+    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    cand, ld, K = _candidates("candidates", candidates, op.B, op.dev)
+    flags = _score_flags(sigmoid, sigmoid_mode, torch.float32, op.bf16)
+    return _candidate_forward(op, cand, ld, K, flags, tables, want_v=False)[0]
+
+
+def score_triples(core, R, S, O, subject_idx, relation_idx, object_idx, sigmoid=True, sigmoid_mode=None, tables=None):
+    """Scores of the triples ``(h, r, t)`` -> ``(B,)``: ``score_candidates`` with K = 1 (the same bits as any column
+    that holds t in a candidate list of the same query)."""
+    dev = core.device if isinstance(core, torch.Tensor) else None
+    t = _idx("object_idx", object_idx, dev) if dev is not None and dev.type == "cuda" else object_idx
+    if not isinstance(t, torch.Tensor):
+        t = torch.as_tensor(t)
+    return score_candidates(core, R, S, O, subject_idx, relation_idx, t.reshape(-1, 1), sigmoid=sigmoid,
+                            sigmoid_mode=sigmoid_mode, tables=tables).view(-1)
 
 
 def cg_fifth_group_columns(N, c, flags=0):
