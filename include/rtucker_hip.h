@@ -539,6 +539,41 @@ int rtk_bce_grad_f32(float *P, int64_t batch, int64_t n_ent, int64_t ld, const i
                      const int64_t *pair_ptr, const int64_t *pair_obj, float label_smoothing,
                      const float *grad_loss, float scale, void *stream);
 
+/*
+ * Filtered ranks without the (batch x n_ent) score matrix (rtk_score_rank.hip).  For query d with object t = obj_idx[d]
+ *   rank[d] = 1 + #{ j : p'_j > p_t } + #{ j < t : p'_j == p_t }
+ * on probabilities (the logistic RTK_SCORE_SIGMOID selects, with or without RTK_SCORE_SIGMOID_FAST; raw logits are not
+ * ranked: flags without RTK_SCORE_SIGMOID give RTK_ERR_UNSUPPORTED), where p' is p with the query's other known-true
+ * objects (pair_obj[pair_ptr[s] .. pair_ptr[s + 1]), s = pair_slot[d] >= 0) set to 0 -- the rule and tie rule of
+ * rtk_filtered_rank_f32.  NaN never counts.  CSR entries outside [0, n_ent) are skipped.  pair_slot may be NULL.
+ *   q_packed   packed query planes of the batch (stage 1, as for rtk_score_packed_*)
+ *   bce_rows   NULL, or per-row BCE sums as rtk_filtered_rank_f32 returns them (every CSR object positive, logs
+ *              clamped at -100); summation order differs, so they agree to ~1e-6 relative.  Reduced in a fixed
+ *              order (no float atomics): repeated calls give the same bits.
+ *   workspace  rtk_score_rank_workspace_bytes (valid without a device), 256-byte aligned; its first word is the
+ *              error word (the workspace of the stage 1 that made q_packed serves, once large enough).
+ * Exactness: each probability is computed with the element arithmetic of the stored kernels, so
+ *   _f32:  ranks equal rtk_filtered_rank_f32 over the scores of rtk_score_packed_f32 with RTK_SCORE_KERNEL_WS and the
+ *          same flags.  The default fp32 dispatch differs from those scores only on the column-group kernel's fifth-group
+ *          columns (rtk_score_fifth_group_columns_f32; none outside 18 432 <= n_ent <= 40 960).
+ *   _bf16: ranks equal rtk_filtered_rank_f32 over rtk_score_packed_bf16's fp32 scores.
+ * A query's rank does not depend on its batch or its position in it.
+ * Covered shapes: _f32 c <= 208, c % 4 == 0, 16-byte-aligned O (the ws kernel's); _bf16 c <= 512.  Others give
+ * RTK_ERR_UNSUPPORTED.  Refused with RTK_ERR_BAD_ARG before anything is enqueued: null pointers, batch < 0,
+ * n_ent < 1, c < 1, pair_slot without the CSR arrays, unknown flags, a workspace too small or not 256-byte aligned.
+ * batch == 0 returns at once.  An object id outside [0, n_ent) sets bit 2 (value 4) of the error word (its rank is
+ * taken against the clamped id).
+ */
+size_t rtk_score_rank_workspace_bytes(int dtype, int64_t batch, int64_t n_ent, int c);
+int rtk_score_rank_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                       const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
+                       const int64_t *pair_obj, unsigned flags, int32_t *ranks, double *bce_rows,
+                       void *workspace, size_t ws_bytes, void *stream);
+int rtk_score_rank_bf16(const void *q_packed, int64_t batch, int c, const void *O, int64_t n_ent,
+                        const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
+                        const int64_t *pair_obj, unsigned flags, int32_t *ranks, double *bce_rows,
+                        void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

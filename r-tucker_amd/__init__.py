@@ -8,7 +8,7 @@ non-GPU tensors, the scoring calls raise.
 """
 from .tucker import Tucker, SFTucker  # noqa: F401
 from .ops import (score_1vN, score_1vN_into, query_vectors, check_device_errors, bce_loss_1vN,  # noqa: F401
-                  relation_tables, index_check, pack_query_vectors, score_packed_into, topk_1vN,
+                  relation_tables, index_check, pack_query_vectors, score_packed_into, topk_1vN, rank_1vN,
                   score_candidates, score_triples)
 from .sharded import EntityShards, ShardedEntityScorer  # noqa: F401
 from . import _lib  # noqa: F401

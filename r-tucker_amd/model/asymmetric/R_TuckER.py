@@ -12,7 +12,7 @@ from __future__ import annotations
 import torch
 from torch import nn
 
-from ...ops import score_1vN, score_candidates, score_triples, topk_1vN
+from ...ops import rank_1vN, score_1vN, score_candidates, score_triples, topk_1vN
 from .._tables import TablesCacheMixin
 
 
@@ -77,3 +77,14 @@ class R_TuckER(TablesCacheMixin, nn.Module):
         if tables is None:
             tables = self._cached_tables(self.core, self.R.weight)
         return topk_1vN(self.core, self.R.weight, self.S.weight, self.O.weight, subject_idx, relation_idx, k, flt=flt, tables=tables, **kw)
+
+    @torch.no_grad()
+    def rank_objects(self, subject_idx, relation_idx, object_idx, flt=None, **kw):
+        """Filtered rank of each ``(subject, relation, object)`` query against every entity (``ops.rank_1vN``;
+        ``want_bce=True`` also returns the BCE row sums).  Relation tables as in ``predict``.  (``self.rank`` is the
+        Tucker rank, as in the reference, hence the name.)"""
+        tables = kw.pop("tables", None)
+        if tables is None:
+            tables = self._cached_tables(self.core, self.R.weight)
+        return rank_1vN(self.core, self.R.weight, self.S.weight, self.O.weight, subject_idx, relation_idx, object_idx, flt=flt,
+                        tables=tables, **kw)

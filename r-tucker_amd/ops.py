@@ -220,6 +220,8 @@ def _check_now(ws, sp):
         raise IndexError("index out of range in self (subject_idx / relation_idx)")
     if flag.value & 2:
         raise IndexError("index out of range in self (candidate id out of range)")
+    if flag.value & 4:
+        raise IndexError("index out of range in self (object_idx out of range)")
 
 
 def _strict_check(ws, sp):
@@ -755,6 +757,44 @@ def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=Non
         # running list first: its ids are all below lo, so tied values stay in ascending id order
         values, ids = (bv, bi) if lo == 0 else filtered_topk(torch.cat([values, bv], 1), k, ids=torch.cat([ids, bi], 1))
     return values, ids
+
+
+@torch.no_grad()
+def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, want_bce=False, sigmoid_mode=None,
+             tables=None):
+    """Filtered rank of each ``(h, r, t)`` query against every entity -> int32 ``(B,)``, or ``(ranks, bce_rows float64)``
+    with ``want_bce`` -- what ``evaluation.filtered_ranks`` gives on ``score_1vN``'s probabilities, without forming the
+    (B, N) score matrix (``rtk_score_rank_*``: one kernel scores and counts, no score is stored).  ``flt`` (a
+    ``DeviceFilter``): the other known-true objects of each query's pair count as probability 0.  Ranks are those of
+    ``filtered_ranks`` over the fp32 ws score kernel's output (bf16 operands: the bf16 kernel's); the default fp32
+    kernel differs from it only on ``cg_fifth_group_columns``.  Inference only.  An ``object_idx`` outside [0, N)
+    raises ``IndexError`` by the ``index_check`` policy."""
+    nt, nh = torch.as_tensor(object_idx).numel(), torch.as_tensor(subject_idx).numel()
+    if nt != nh:
+        raise RuntimeError(f"object_idx has {nt} entries for {nh} queries")
+    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    B, N, dev = op.B, op.O.shape[0], op.dev
+    t = _idx("object_idx", object_idx, dev)
+    flags = _score_flags(True, sigmoid_mode, torch.float32, op.bf16)
+    ranks = torch.empty(B, dtype=torch.int32, device=dev)
+    bce = torch.empty(B, dtype=torch.float64, device=dev) if want_bce else None
+    if B == 0:
+        return (ranks, bce) if want_bce else ranks
+    slots = flt.slots_of(op.h, op.r) if flt is not None else None
+    with torch.cuda.device(dev):
+        sp = _stream_ptr(dev)
+        qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.c))
+        _stage1(op, sp, tables, None, qp)
+        ws = _workspace(dev, sp, _size("rtk_score_rank_workspace_bytes", op.dcode, B, N, op.c))
+        _lib.check(_entry("rtk_score_rank", op.bf16)(
+            qp.data_ptr(), B, op.c, op.O.data_ptr(), N, t.data_ptr(),
+            slots.data_ptr() if slots is not None else None,
+            flt.pair_ptr.data_ptr() if slots is not None else None,
+            flt.pair_obj.data_ptr() if slots is not None else None,
+            flags, ranks.data_ptr(), bce.data_ptr() if want_bce else None, ws.data_ptr(), ws.numel(), sp),
+            "rtk_score_rank")
+        _strict_check(ws, sp)
+    return (ranks, bce) if want_bce else ranks
 
 
 def _candidates(name, t, B, dev):
