@@ -574,6 +574,52 @@ int rtk_score_rank_bf16(const void *q_packed, int64_t batch, int c, const void *
                         const int64_t *pair_obj, unsigned flags, int32_t *ranks, double *bce_rows,
                         void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * The same ranking on one block of entity rows (an entity shard), without the (batch x n_local) score block
+ * (rtk_score_rank_part.hip): the matrix-free twins of rtk_target_scores_f32 / rtk_filtered_rank_partial_f32.  The
+ * caller holds rows [col0, col0 + n_local) of the (n_ent x c) entity matrix as O_local; obj_idx and pair_obj hold
+ * GLOBAL entity ids.
+ *   1. rtk_score_rank_targets_*: pt_out[d] = probability of (query d, obj_idx[d]) where the block owns the object
+ *      (col0 <= obj_idx[d] < col0 + n_local, the id clamped into [0, n_ent) first), -inf elsewhere; all-reduce MAX
+ *      over the ranks completes it.  An id outside [0, n_ent) sets bit 2 of the error word.
+ *   2. rtk_score_rank_counts_*: counts_out[d] = this block's share of
+ *      #{j : p'_j > pt[d]} + #{j < t : p'_j == pt[d]}, j = col0 + row, with the rule, tie rule and filter rule of
+ *      rtk_score_rank_* (the query's other CSR objects count as probability 0, the queried object is never
+ *      counted, NaN never counts, CSR entries outside the block are ignored; the CSR lists each object once);
+ *      bce_rows_out (optional): its share of the row's BCE sum.  All-reduce SUM, then rank = 1 + count.
+ * Element arithmetic is that of rtk_score_rank_* (one shared implementation), so for every partition of [0, n_ent)
+ * into blocks 1 + the sum of the blocks' counts EQUALS the ranks of rtk_score_rank_* on the whole range, in both
+ * logistic modes, and pt after the MAX has the bits of that call's internal target score.  The BCE shares sum to
+ * its bce_rows to ~1e-6 relative; they are reduced in a fixed order (no float atomics): repeated calls give the
+ * same bits.
+ * The dense pass of step 2 is entity-stationary: every row of O_local is converted into MFMA operands once per
+ * call (once per query range when n_local < 65 536), not once per 32-query tile.
+ * Workspace: rtk_score_rank_part_workspace_bytes (valid without a device), 256-byte aligned, for both steps:
+ *     256 + 2 * align256(4 * S * batch) + 2 * align256(4 * 8 * batch),   S = min(512, ceil(n_local / 128)),
+ * align256 rounding up to a multiple of 256: partial counts and BCE sums per resident workgroup (at most two per
+ * CU) and per filter wave (8 per query); nothing grows with batch * n_local (34.1 MB at batch 8192,
+ * n_local 125 000).  Its first word is the error word.
+ * Covered shapes, flags and refusals as rtk_score_rank_*; in addition col0 < 0, n_local < 1 or
+ * col0 + n_local > n_ent give RTK_ERR_BAD_ARG.  batch == 0 returns at once.
+ */
+size_t rtk_score_rank_part_workspace_bytes(int dtype, int64_t batch, int64_t n_local, int c);
+int rtk_score_rank_targets_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                               int64_t col0, int64_t n_ent, const int64_t *obj_idx, unsigned flags, float *pt_out,
+                               void *workspace, size_t ws_bytes, void *stream);
+int rtk_score_rank_targets_bf16(const void *q_packed, int64_t batch, int c, const void *O_local, int64_t n_local,
+                                int64_t col0, int64_t n_ent, const int64_t *obj_idx, unsigned flags, float *pt_out,
+                                void *workspace, size_t ws_bytes, void *stream);
+int rtk_score_rank_counts_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                              int64_t col0, int64_t n_ent, const float *pt, const int64_t *obj_idx,
+                              const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                              unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
+                              size_t ws_bytes, void *stream);
+int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, int c, const void *O_local, int64_t n_local,
+                               int64_t col0, int64_t n_ent, const float *pt, const int64_t *obj_idx,
+                               const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                               unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
+                               size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -89,6 +89,11 @@ SIGNATURES = {
     "rtk_score_rank_workspace_bytes": (_sz, [_i, _i64, _i64, _i]),
     "rtk_score_rank_f32": (_i, [_p, _i64, _i, _p, _i64, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
     "rtk_score_rank_bf16": (_i, [_p, _i64, _i, _p, _i64, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
+    "rtk_score_rank_part_workspace_bytes": (_sz, [_i, _i64, _i64, _i]),
+    "rtk_score_rank_targets_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _u, _p, _p, _sz, _p]),
+    "rtk_score_rank_targets_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _u, _p, _p, _sz, _p]),
+    "rtk_score_rank_counts_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
+    "rtk_score_rank_counts_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -797,6 +797,102 @@ def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, wan
     return (ranks, bce) if want_bce else ranks
 
 
+class _Block:
+    """The checked operands of a ranking step on one entity block: packed query planes of ``B`` queries, the block's
+    rows ``O_loc`` of the (n_ent, c) entity matrix starting at global row ``col0``, the queries' object ids."""
+    __slots__ = ("qp", "B", "O", "n_loc", "c", "col0", "n_ent", "t", "dev", "bf16", "dcode")
+
+    def __init__(self, qp, B, O_loc, col0, n_ent, object_idx):
+        _require_gpu("O_loc", O_loc)
+        _require_gpu("q_packed", qp)
+        if O_loc.dtype not in (torch.float32, torch.bfloat16) or O_loc.dim() != 2:
+            raise RuntimeError(f"O_loc must be a float32 or bfloat16 (n_local, c) matrix, got {O_loc.dtype} "
+                               f"{tuple(O_loc.shape)}")
+        self.dev = dev = O_loc.device
+        self.bf16 = O_loc.dtype == torch.bfloat16
+        self.dcode = _dtype_code(self.bf16)
+        self.O = O_loc.contiguous()
+        self.n_loc, self.c = self.O.shape
+        self.B, self.col0, self.n_ent = int(B), int(col0), int(n_ent)
+        if self.B < 0:
+            raise RuntimeError(f"B = {B} must be >= 0")
+        need = _size("rtk_packed_query_bytes", self.dcode, self.B, self.c)
+        if qp.dtype != torch.uint8 or qp.device != dev or not qp.is_contiguous() or qp.numel() < need:
+            raise RuntimeError(f"q_packed must be a contiguous uint8 tensor of >= {need} bytes on {dev} "
+                               "(query_vectors(..., packed=True) / pack_query_vectors)")
+        self.qp = qp
+        if self.col0 < 0 or self.n_loc < 1 or self.col0 + self.n_loc > self.n_ent:
+            raise RuntimeError(f"block [{self.col0}, {self.col0} + {self.n_loc}) is not a non-empty part of "
+                               f"[0, n_ent = {self.n_ent})")
+        nt = torch.as_tensor(object_idx).numel()
+        if nt != self.B:
+            raise RuntimeError(f"object_idx has {nt} entries for {self.B} queries")
+        self.t = _idx("object_idx", object_idx, dev)
+
+    def workspace(self, sp):
+        return _workspace(self.dev, sp, _size("rtk_score_rank_part_workspace_bytes", self.dcode, self.B, self.n_loc, self.c))
+
+
+@torch.no_grad()
+def rank_targets_block(qp, B, O_loc, col0, n_ent, object_idx, sigmoid_mode=None):
+    """Step 1 of the matrix-free ranking on an entity block (``rtk_score_rank_targets_*``): ``pt[d]`` = probability of
+    ``(query d, object_idx[d])`` where ``col0 <= object_idx[d] < col0 + n_local``, ``-inf`` elsewhere -> float32 ``(B,)``.
+    ``qp``: packed query planes (``query_vectors(..., packed=True)`` / ``pack_query_vectors``); ``O_loc``: rows
+    ``[col0, col0 + n_local)`` of the (n_ent, c) entity matrix; ``object_idx``: GLOBAL ids.  The maximum over the
+    blocks completes ``pt``.  An id outside [0, n_ent) raises ``IndexError`` by the ``index_check`` policy."""
+    b = _Block(qp, B, O_loc, col0, n_ent, object_idx)
+    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
+    pt = torch.empty(b.B, dtype=torch.float32, device=b.dev)
+    if b.B == 0:
+        return pt
+    with torch.cuda.device(b.dev):
+        sp = _stream_ptr(b.dev)
+        ws = b.workspace(sp)
+        _lib.check(_entry("rtk_score_rank_targets", b.bf16)(
+            b.qp.data_ptr(), b.B, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent, b.t.data_ptr(), flags, pt.data_ptr(),
+            ws.data_ptr(), ws.numel(), sp), "rtk_score_rank_targets")
+        _strict_check(ws, sp)
+    return pt
+
+
+@torch.no_grad()
+def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, slots=None, want_bce=False,
+                          sigmoid_mode=None):
+    """Step 2 (``rtk_score_rank_counts_*``): this block's share of the rank count -> int32 ``(B,)``, or
+    ``(counts, bce_rows float64)`` with ``want_bce``; nothing of size B x n_local is written.  ``pt``: the completed
+    target scores (float32, B).  ``flt`` (a ``DeviceFilter``) with ``slots`` (``flt.slots_of(h, r)``): the queries'
+    other known-true objects count as probability 0.  Summed over any partition of [0, n_ent) into blocks,
+    ``1 + counts`` equals ``rank_1vN``'s ranks exactly."""
+    b = _Block(qp, B, O_loc, col0, n_ent, object_idx)
+    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
+    if (not isinstance(pt, torch.Tensor) or pt.dtype != torch.float32 or pt.device != b.dev or pt.numel() != b.B):
+        raise RuntimeError(f"pt must be a float32 tensor of {b.B} target scores on {b.dev}")
+    pt = pt.contiguous().view(-1)
+    if flt is not None:
+        if slots is None:
+            raise ValueError("filtering needs the queries' filter slots: slots=flt.slots_of(subject_idx, relation_idx)")
+        slots = _idx("slots", slots, b.dev)
+        if slots.numel() != b.B:
+            raise RuntimeError(f"slots has {slots.numel()} entries for {b.B} queries")
+    elif slots is not None:
+        raise ValueError("slots need flt (the DeviceFilter that holds the CSR)")
+    counts = torch.empty(b.B, dtype=torch.int32, device=b.dev)
+    bce = torch.empty(b.B, dtype=torch.float64, device=b.dev) if want_bce else None
+    if b.B == 0:
+        return (counts, bce) if want_bce else counts
+    with torch.cuda.device(b.dev):
+        sp = _stream_ptr(b.dev)
+        ws = b.workspace(sp)
+        _lib.check(_entry("rtk_score_rank_counts", b.bf16)(
+            b.qp.data_ptr(), b.B, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent, pt.data_ptr(), b.t.data_ptr(),
+            slots.data_ptr() if flt is not None else None,
+            flt.pair_ptr.data_ptr() if flt is not None else None,
+            flt.pair_obj.data_ptr() if flt is not None else None,
+            flags, counts.data_ptr(), bce.data_ptr() if want_bce else None, ws.data_ptr(), ws.numel(), sp),
+            "rtk_score_rank_counts")
+    return (counts, bce) if want_bce else counts
+
+
 def _candidates(name, t, B, dev):
     """``(tensor, ld_cand, K)`` of a (B, K) int64 candidate matrix on ``dev`` with unit column stride; a row broadcast
     over the batch (``cand.expand(B, K)``, row stride 0) is one shared list (``ld_cand = 0``)."""

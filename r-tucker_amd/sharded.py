@@ -85,6 +85,7 @@ class ShardedEntityScorer:
         self._v_all = None
         self._v_rel = None
         self.query_vectors_part_fn = None       # tests inject a CPU function for stage1="relation"
+        self.pack_fn = None                     # tests inject a CPU stand-in for ops.pack_query_vectors (rank_1vN)
         # the score exchange: "torch" = torch.distributed's all_gather_into_tensor on the process group (RCCL when
         # the backend is "nccl"); "abi" = the C ABI's own communicator (rtk_comm_init / rtk_allgather_scores:
         # RCCL bound by the library itself -- the path a non-Python host takes; torch.distributed only carries the
@@ -261,6 +262,64 @@ class ShardedEntityScorer:
         else:
             counts = torch.zeros(B, dtype=torch.int32, device=core.device)
             bce = torch.zeros(B, dtype=torch.float64, device=core.device) if want_bce else None
+        if self.world > 1:
+            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
+            if want_bce:
+                dist.all_reduce(bce, op=dist.ReduceOp.SUM, group=self.group)
+        ranks = counts + 1
+        return (ranks, bce) if want_bce else ranks
+
+    # ---- ranking without the gather and without the score block --------------------------------
+    def _packed_queries(self, core, R, S, dtype, subject_idx, relation_idx, tables):
+        """Packed query planes of the batch, stage 1 by the scorer's policy (replicated, "split", "relation")."""
+        qkw = {"tables": tables} if tables is not None else {}
+        if self._split_stage1(core):
+            if self.stage1 == "relation" and tables is not None:
+                v = self.query_vectors_by_relation(core, R, S, subject_idx, relation_idx, tables)
+            else:
+                v = self.query_vectors_split(core, R, S, subject_idx, relation_idx, **qkw)
+        elif self.query_vectors_fn is not None:
+            v = self.query_vectors_fn(core, R, S, subject_idx.view(-1), relation_idx.view(-1), **qkw)
+        else:
+            from .ops import query_vectors
+            return query_vectors(core, R, S, subject_idx, relation_idx, packed=True, **qkw)[1]
+        pack = self.pack_fn
+        if pack is None:
+            from .ops import pack_query_vectors as pack
+        return pack(v, dtype)
+
+    def rank_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt=None, want_bce=False, tables=None,
+                 sigmoid_mode=None, targets_fn=None, counts_fn=None):
+        """``filtered_ranks`` without the (B, n_loc) score block: stage 1 once into packed query planes, the target
+        scores of this rank's rows (``ops.rank_targets_block``) completed by one all-reduce(MAX) of B floats, the
+        block's counts (``ops.rank_counts_block_1vN``: scored and counted in one entity-stationary pass) by one
+        all-reduce(SUM) of B int32 (+ B doubles for the BCE sums); rank = count + 1.  ``object_idx`` and the filter
+        hold global entity ids.  Equals ``ops.rank_1vN`` on the whole entity matrix exactly.
+
+        ``targets_fn`` / ``counts_fn`` take the arguments of the two ``ops`` functions; tests inject CPU functions
+        (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
+        if targets_fn is None or counts_fn is None:
+            from .ops import rank_counts_block_1vN, rank_targets_block
+            targets_fn = targets_fn or rank_targets_block
+            counts_fn = counts_fn or rank_counts_block_1vN
+        B = int(subject_idx.numel())
+        dev = core.device
+        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
+        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
+        slots = flt.slots_of(subject_idx, relation_idx) if flt is not None else None
+        qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)
+        rows = O_loc[:n_valid] if n_valid > 0 else None
+        pt = (targets_fn(qp, B, rows, lo, self.shards.n_ent, object_idx, sigmoid_mode=sigmoid_mode) if rows is not None
+              else torch.full((B,), float("-inf"), dtype=torch.float32, device=dev))
+        if self.world > 1:
+            dist.all_reduce(pt, op=dist.ReduceOp.MAX, group=self.group)
+        if rows is not None:
+            res = counts_fn(qp, B, rows, lo, self.shards.n_ent, pt, object_idx, flt=flt, slots=slots, want_bce=want_bce,
+                            sigmoid_mode=sigmoid_mode)
+            counts, bce = res if want_bce else (res, None)
+        else:
+            counts = torch.zeros(B, dtype=torch.int32, device=dev)
+            bce = torch.zeros(B, dtype=torch.float64, device=dev) if want_bce else None
         if self.world > 1:
             dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
             if want_bce:
