@@ -620,6 +620,60 @@ int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, int c, const
                                unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
                                size_t ws_bytes, void *stream);
 
+/*
+ * The 1-vs-all BCE training loss and its gradients WITHOUT the (batch x n_ent) score matrix (rtk_bce_stream.hip): the
+ * matrix-free form of rtk_score_packed_bce_f32 + rtk_bce_patch_pos_f32 and of the two batch x n_ent sized GEMMs of the
+ * backward.  Same arithmetic: p = the ws score kernel's probability (Frag of rtk_score_rank_*, both logistic modes),
+ * targets y = (1 - eps) * multi_hot + eps / n_ent with the multi-hot part given as the CSR (pair_slot[d] < 0: an empty
+ * list; entries outside [0, n_ent) are skipped; every object of a pair once), logs clamped at -100, and the logit
+ * gradient x = p - y, 0 where the fp32 p is exactly 1.0f or 0.0f.
+ *   rtk_bce_stream_rows_f32    loss_rows_out[d] = sum_j BCE(p[d, j], y[d, j]) (float64; loss = sum / (batch n_ent)) and,
+ *                              when dv_out is given, dv_out[d, :] = sum_j x[d, j] O[j, :] (batch x c, UNSCALED: multiply
+ *                              by g / (batch n_ent) before rtk_query_vectors_bwd_f32).  dv_out NULL: the second tile
+ *                              product is not computed.
+ *   rtk_bce_stream_grad_o_f32  gO_out[j, :] = sum_d x[d, j] * scale[0] * v[d, :], all n_ent x c written (rows that no
+ *                              term touches are 0).  v: the fp32 query vectors (batch x c); scale: one float on the
+ *                              device (g / (batch n_ent)).
+ * Both sweep all (query tile, entity tile) pairs once; the 32 x 32 tile of x is never stored but used as the operand
+ * of the next MFMA: in sweep 1 (rows) the query is on the lane and the tile is the A operand of X O, in sweep 2
+ * (grad_o) the entity is on the lane and the tile is the A operand of X^T V.  Both products are three f16 MFMAs per
+ * k-step on hi/lo halves with fp32 accumulation (x scaled by 2^14; O and scale * v by the power of two that brings
+ * their largest magnitude into [2^14, 2^15)): the accuracy class of rtk_gemm_sf16_splitk.
+ * Summation orders (no float atomics; repeated calls give the same bits):
+ *   rows:   a workgroup holds 128 queries and walks a contiguous range of 32-row entity tiles in increasing order; the
+ *           entity tiles are cut into `splits` = max(1, 256 / ceil(batch / 128)) ranges -- a function of batch and the
+ *           CU count only -- whose dv slabs and loss partials (one float sum per tile and lane, added in float64) are
+ *           added in range order.  The positives are added last (per query: its CSR entries in four interleaved
+ *           groups of 32, the groups in order).  A query's row of loss_rows and dv does not depend on the other
+ *           queries of the batch or on its position within them (only on batch through `splits`).
+ *   grad_o: a wave owns 32 rows of gO and adds the query tiles in increasing order onto the positives' share, which
+ *           rtk_score_candidates_bwd's ordered scatter builds (stable sort by entity, fixed chunk order).
+ * max_pos: an upper bound, known to the host, on the number of CSR entries of the batch's queries (a query counted
+ * as often as it occurs); the ordered scatter's buffers have that size.  More entries than that set bit 3 (value 8) of
+ * the error word and the surplus is dropped.  rtk_bce_stream_rows_f32 needs no such bound (workspace for max_pos = 0).
+ * Workspace: rtk_bce_stream_workspace_bytes(batch, n_ent, c, max_pos), valid without a device, 256-byte aligned; with
+ * cp = 32 * ceil(c / 32), S = splits and align256 rounding up to a multiple of 256:
+ *     512 + align256(8 S batch) + align256(32 batch) + align256(4 S batch cp) + 2 align256(4 batch c)
+ *         + align256(128 cp ceil(batch / 32)) + align256(4 (batch + 1)) + 3 align256(4 max_pos)
+ *         + the ordered scatter's buffers for max_pos entries (rtk_score_candidates_bwd_workspace_bytes(max_pos, 1, .)),
+ * nothing of which grows with batch * n_ent (about 95 MB at batch 4096, c 200, max_pos 1 000 000, any n_ent).  Its
+ * first word is the error word.
+ * Covered shapes: fp32, c <= 208, c % 4 == 0, 16-byte-aligned O (the range of rtk_score_rank_f32); others give
+ * RTK_ERR_UNSUPPORTED -- there is no fallback to the matrix form.  flags: RTK_SCORE_SIGMOID, optionally
+ * RTK_SCORE_SIGMOID_FAST.  Refused with RTK_ERR_BAD_ARG before anything is enqueued: null pointers, negative sizes,
+ * label smoothing outside [0, 1), unknown flags, a workspace too small or not 256-byte aligned.  batch == 0: rows
+ * returns at once, grad_o zeroes gO_out.  Enqueue only on `stream`; graph-capturable.
+ */
+size_t rtk_bce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos);
+int rtk_bce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                            const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                            float label_smoothing, unsigned flags, double *loss_rows_out, float *dv_out,
+                            void *workspace, size_t ws_bytes, void *stream);
+int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O,
+                              int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                              const int64_t *pair_obj, int64_t max_pos, float label_smoothing, unsigned flags,
+                              const float *scale, float *gO_out, void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

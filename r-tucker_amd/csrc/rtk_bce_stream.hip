@@ -1,0 +1,718 @@
+// The 1-vs-all BCE training loss and its gradients without the (B, N) score matrix: the matrix-free form of
+// rtk_score_packed_bce_f32 + rtk_bce_patch_pos_f32 (forward) and of the two B x N sized GEMMs of the backward.
+// Everything is linear in the upstream gradient, so the sweeps work on the unscaled logit gradient of a negative,
+//
+//     x[d, j] = p[d, j] - eps / N        (0 where the fp32 p is exactly 1.0f or 0.0f),
+//
+// and the positives (the CSR entries, whose target is eps / N + (1 - eps)) are a sparse correction:
+//
+//   rows_kernel   sweep 1.  The score tile is computed with the QUERY on the lane and the entities in the accumulator
+//                 registers (entity fragments as the A operand, the packed query planes as B), so the 32 x 32 tile of x is
+//                 the A operand of the next product, dv[d, :] += sum_j x[d, j] O[j, :], with no lane movement.  A
+//                 workgroup of 4 waves holds 4 query tiles (fragments and the dv accumulators in registers) and sweeps
+//                 a range of 32-row entity tiles; each tile is converted once per workgroup into LDS in two layouts
+//                 (the chain's operand with the per-row scaling of Frag, and the k-permuted transposed operand of the
+//                 dv product with one scale for all of O).  The BCE terms of the tile are summed per query.  The entity
+//                 range is cut into `splits` parts; slabs and loss partials are added by finish_kernel in split order.
+//   go_kernel     sweep 2, count_kernel's skeleton (rtk_score_rank_part.hip): a wave converts its 32 entity rows once,
+//                 sweeps the query tiles staged through LDS together with the packed tile of s v, and accumulates
+//                 gO[j, :] += sum_d x[d, j] (s v[d, :]).  Here the entity is on the lane and the tile is the A operand
+//                 of X^T V.  A wave owns its 32 rows of gO: one read-add-store on top of the positives' share.
+//   pos_kernel    the positives: one workgroup per query re-scores the query's CSR entries with Frag (the sweeps' bits),
+//                 gives the loss correction -(1 - eps) (ln p - ln(1 - p)), the positives' share of dv, and the flat
+//                 (entity, query, dz) lists that the ordered scatter of rtk_candidates.hip turns into their share of gO.
+//
+// Both tile products are three f16 MFMAs per k-step on hi/lo halves (x scaled by 2^14; O and s v by a power of two from
+// their largest magnitude), accumulated in fp32.  No float atomics: every sum has a fixed order.
+#include "rtk_common.h"
+#include "rtk_pack.h"
+#include "rtk_score_rank_kernel.h"
+#include "rtk_score_select.h"
+
+// the flat front end of the ordered scatter (rtk_candidates.hip)
+size_t rtk_cand_flat_workspace_bytes(int64_t m);
+int rtk_cand_flat_scatter(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m,
+                          int64_t n_ent, const float *v, int c, float *gO, void *workspace, hipStream_t st);
+
+namespace {
+
+constexpr int BS_WAVES = 4;
+constexpr int BS_MAX_KS = RTK_CG_MAX_KS;       // Frag<float, KS>'s range: c <= 208
+constexpr int BS_POS_Y = 4;                    // loss partials per query of pos_kernel (one per wave)
+constexpr float BS_X_UP = 16384.0f;            // |x| <= 1 scaled to 2^14 before the hi/lo split
+
+__host__ __device__ constexpr int nct_of(int ks) { return (ks + 1) / 2; }       // 32-column tiles of 16 ks columns
+// bytes of the transposed image of a 32-row tile: [plane][column tile][k-step][lane][8 halves]
+__host__ __device__ constexpr int timg_bytes(int ks) { return nct_of(ks) * 4096; }
+
+// index, in halves, of element (row j of the tile, column col) in plane 0 of the transposed image: lane (col & 31, h)
+// holds in k-step t the rows 16 t + 8 (q >> 2) + 4 h + (q & 3), q = 0..7 -- the order in which an accumulator tile
+// supplies its rows as an operand
+__device__ __forceinline__ int timg_index(int j, int col) {
+    const int t = j >> 4, q = ((j >> 3) & 1) * 4 + (j & 3), h = (j >> 2) & 1;
+    return ((((col >> 5) * 2 + t) * 64) + h * 32 + (col & 31)) * 8 + q;
+}
+
+__device__ __forceinline__ f32x16 zero16() {
+    return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+}
+
+// x of one probability and its BCE term as a negative
+__device__ __forceinline__ float x_of(float p, float t0, bool valid) {
+    return (valid && p != 1.0f && p != 0.0f) ? p - t0 : 0.0f;
+}
+
+// the 16 values of a tile held by a lane, scaled and split into the two k-steps' operand fragments
+__device__ __forceinline__ void split_x(const float (&x)[16], f16x8 (&xh)[2], f16x8 (&xl)[2]) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const float y = x[8 * t + q] * BS_X_UP;
+            const _Float16 hi = (_Float16)y;
+            xh[t][q] = hi;
+            xl[t][q] = (_Float16)(y - (float)hi);
+        }
+}
+
+// acc[ct] += X * T for the transposed image `timg` (plane stride in 16-byte units: NCT * 128)
+template <int NCT>
+__device__ __forceinline__ void tile_product(const f16x8 (&xh)[2], const f16x8 (&xl)[2], const f16x8 *__restrict__ timg,
+                                             int lane, f32x16 (&acc)[NCT]) {
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            const f16x8 bh = timg[(ct * 2 + t) * 64 + lane], bl = timg[(NCT * 2 + ct * 2 + t) * 64 + lane];
+            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[t], bh, acc[ct], 0, 0, 0);
+            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[t], bl, acc[ct], 0, 0, 0);
+            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[t], bh, acc[ct], 0, 0, 0);
+        }
+}
+
+template <int KS>
+struct RowsLds {
+    static constexpr int NCT = nct_of(KS);
+    static constexpr int A1 = 0;                       // [2][KS][64] x 16 B: the tile's rows as the chain's operand
+    static constexpr int T2 = 2 * KS * 1024;           // the transposed image of the same rows (one scale for all of O)
+    static constexpr int KC = T2 + timg_bytes(KS);     // 32 floats: Frag's kcol of the rows
+    static constexpr int TOTAL = KC + 128;
+};
+
+// Sweep 1.  Workgroup (qg, sp): query tiles 4 qg .. 4 qg + 3 (one per wave), entity tiles of split sp.
+template <int KS, int SG, bool DV>
+__global__ __launch_bounds__(64 * BS_WAVES, 1) void rows_kernel(const unsigned char *__restrict__ qp, int B,
+                                                                const float *__restrict__ O, int N, int c, float t0,
+                                                                const float *__restrict__ o_bound, int n_splits,
+                                                                double *__restrict__ part_loss,
+                                                                float *__restrict__ slab) {
+    typedef RowsLds<KS> L;
+    constexpr int NCT = L::NCT, CP = 32 * NCT;
+    constexpr int NF = (4 * KS + 7) / 8;               // float4 pieces of a row per staging thread
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int qg = (int)blockIdx.x / n_splits, sp = (int)blockIdx.x % n_splits;
+    const int n_mt = (B + 31) >> 5, n_t = (N + 31) >> 5;
+    const int mt = qg * BS_WAVES + wave;
+    const bool active = mt < n_mt;                                  // (wave-uniform)
+    const int tb = (int)((int64_t)n_t * sp / n_splits), te = (int)((int64_t)n_t * (sp + 1) / n_splits);
+
+    f16x8 Qh[KS], Ql[KS];
+    float srow = 1.0f;
+    if (active) {
+        load_a<float, KS>(qp, mt, r, h, Qh, Ql);
+        srow = reinterpret_cast<const float *>(qp + mt * tile_bytes<float, KS>())[r];
+    } else {
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) Qh[ks] = Ql[ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    }
+    f32x16 dacc[NCT];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct) dacc[ct] = zero16();
+    double lsum = 0.0;
+    const float up2 = DV ? ldexpf(1.0f, rtk_pack_shift(o_bound[0])) : 1.0f;
+
+    // staging: 8 consecutive threads take one row, thread `part` the float4 pieces part, part + 8, ...
+    const int srw = t >> 3, part = t & 7;
+    f32x4 stg[NF];
+    auto stage_load = [&](int tile) {
+        const float *row = O + (int64_t)min(tile * 32 + srw, N - 1) * c;
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int k0 = 4 * (part + 8 * i);
+            stg[i] = (k0 + 4 <= c) ? *reinterpret_cast<const f32x4 *>(row + k0) : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+    };
+    auto stage_store = [&]() {
+        float mx = 0.f;
+#pragma unroll
+        for (int i = 0; i < NF; ++i)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) mx = fmaxf(mx, fabsf(stg[i][q]));
+        mx = fmaxf(mx, __shfl_xor(mx, 1));
+        mx = fmaxf(mx, __shfl_xor(mx, 2));
+        mx = fmaxf(mx, __shfl_xor(mx, 4));
+        const int sh = rtk_pack_shift(mx);                          // Frag::convert's scaling of the row
+        const float up = ldexpf(1.0f, sh), us_o = ldexpf(1.0f, -sh);
+        if (part == 0) reinterpret_cast<float *>(lds + L::KC)[srw] = SG == 2 ? us_o * -1.4426950408889634f : us_o;
+        _Float16 *t2 = reinterpret_cast<_Float16 *>(lds + L::T2);
+#pragma unroll
+        for (int i = 0; i < NF; ++i) {
+            const int f = part + 8 * i;
+            if (f >= 4 * KS) continue;
+            const int ks = f >> 2, hh = (f >> 1) & 1, q0 = (f & 1) * 4;
+            f16x4 hi, lo;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float y = stg[i][q] * up;
+                const _Float16 y0 = (_Float16)y;
+                hi[q] = y0;
+                lo[q] = (_Float16)(y - (float)y0);
+            }
+            const int at = (ks * 64 + hh * 32 + srw) * 16 + q0 * 2;
+            *reinterpret_cast<f16x4 *>(lds + L::A1 + at) = hi;
+            *reinterpret_cast<f16x4 *>(lds + L::A1 + KS * 1024 + at) = lo;
+            if (DV) {                                               // (columns past 16 KS stay unwritten: they feed output columns >= c, never stored)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float y = stg[i][q] * up2;
+                    const _Float16 y0 = (_Float16)y;
+                    const int ix = timg_index(srw, 4 * f + q);
+                    t2[ix] = y0;
+                    t2[NCT * 1024 + ix] = (_Float16)(y - (float)y0);
+                }
+            }
+        }
+    };
+
+    if (tb < te) stage_load(tb);
+    for (int tile = tb; tile < te; ++tile) {
+        stage_store();
+        __syncthreads();
+        if (tile + 1 < te) stage_load(tile + 1);
+        if (active) {
+            const f16x8 *la = reinterpret_cast<const f16x8 *>(lds + L::A1);
+            f32x16 acc;
+#pragma unroll
+            for (int ks = 0; ks < KS; ++ks) {                       // Frag::chain's products with the roles swapped
+                const f16x8 eh = la[ks * 64 + lane], el = la[(KS + ks) * 64 + lane];
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(eh, Qh[ks], ks == 0 ? zero16() : acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(el, Qh[ks], acc, 0, 0, 0);
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(eh, Ql[ks], acc, 0, 0, 0);
+            }
+            // element e: entity row 8 (e / 4) + 4 h + e % 4 of the tile, query r of the wave
+            float x[16];
+            float ls = 0.f;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 kc4 = *reinterpret_cast<const f32x4 *>(lds + L::KC + (8 * g + 4 * h) * 4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int e = 4 * g + q;
+                    const bool valid = tile * 32 + 8 * g + 4 * h + q < N;
+                    const float s = srow * kc4[q];                  // Frag::prob
+                    const float p = SG == 2 ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[e] * s))
+                                            : rtk_sigmoid(acc[e] * s);
+                    x[e] = x_of(p, t0, valid);
+                    ls += valid ? t0 * clog(p) + (1.0f - t0) * clog(1.0f - p) : 0.f;
+                }
+            }
+            lsum += (double)ls;
+            if (DV) {
+                f16x8 xh[2], xl[2];
+                split_x(x, xh, xl);
+                tile_product<NCT>(xh, xl, reinterpret_cast<const f16x8 *>(lds + L::T2), lane, dacc);
+            }
+        }
+        __syncthreads();
+    }
+    if (!active) return;
+    lsum += __shfl_xor(lsum, 32);
+    const int d = mt * 32 + r;
+    if (h == 0 && d < B) part_loss[(int64_t)sp * B + d] = lsum;
+    if (DV) {
+        // element e of dacc[ct]: query row 8 (e / 4) + 4 h + e % 4 of the tile, column 32 ct + r
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int dq = mt * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+                if (dq < B) slab[((int64_t)sp * B + dq) * CP + ct * 32 + r] = dacc[ct][e];
+            }
+    }
+}
+
+// loss_rows[d] = -(the splits' partial sums, in split order) + the positives' correction;
+// dv[d, :] = (the splits' slabs, in split order) * 2^-(14 + sh_O) + the positives' share.  One workgroup per query.
+__global__ __launch_bounds__(256) void rows_finish_kernel(int B, int c, int cp, int n_splits,
+                                                          const double *__restrict__ part_loss,
+                                                          const double *__restrict__ rows_pos,
+                                                          const float *__restrict__ slab, const float *__restrict__ dvpos,
+                                                          const float *__restrict__ o_bound,
+                                                          double *__restrict__ loss_rows, float *__restrict__ dv) {
+    const int d = blockIdx.x, t = threadIdx.x;
+    if (t == 0) {
+        double s = 0.0;
+        for (int k = 0; k < n_splits; ++k) s += part_loss[(int64_t)k * B + d];
+        double pcor = 0.0;
+#pragma unroll
+        for (int u = 0; u < BS_POS_Y; ++u) pcor += rows_pos[(int64_t)d * BS_POS_Y + u];
+        loss_rows[d] = -s + pcor;
+    }
+    if (dv && t < c) {
+        const float un = ldexpf(1.0f, -14 - rtk_pack_shift(o_bound[0]));
+        float s = 0.f;
+        for (int k = 0; k < n_splits; ++k) s += slab[((int64_t)k * B + d) * cp + t];
+        dv[(int64_t)d * c + t] = s * un + dvpos[(int64_t)d * c + t];
+    }
+}
+
+// off[d] = entries of the queries before d in the flat lists (exclusive prefix of the CSR list lengths), off[B] = all.
+__global__ __launch_bounds__(256) void pos_offsets_kernel(int B, const int64_t *__restrict__ pair_slot,
+                                                          const int64_t *__restrict__ pair_ptr, int64_t max_pos,
+                                                          int32_t *__restrict__ off, uint32_t *__restrict__ err) {
+    __shared__ long long wsum[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    long long carry = 0;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int d = b0 + t;
+        long long len = 0;
+        if (d < B) {
+            const int64_t s = pair_slot[d];
+            if (s >= 0) len = pair_ptr[s + 1] - pair_ptr[s];
+            if (len < 0) len = 0;
+        }
+        long long inc = len;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long y = __shfl_up(inc, o);
+            if (lane >= o) inc += y;
+        }
+        if (lane == 63) wsum[wv] = inc;
+        __syncthreads();
+        long long before = 0, tot = 0;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            before += i < wv ? wsum[i] : 0;
+            tot += wsum[i];
+        }
+        __syncthreads();
+        const long long ex = carry + before + inc - len;
+        if (d < B) off[d] = (int32_t)(ex < max_pos ? ex : max_pos);
+        carry += tot;
+    }
+    if (t == 0) {
+        off[B] = (int32_t)(carry < max_pos ? carry : max_pos);
+        if (carry > max_pos) atomicOr(err, 8u);                   // the lists are longer than the caller's bound
+    }
+}
+
+__global__ __launch_bounds__(256) void pos_fill_kernel(int64_t m, int32_t n_ent, int32_t *__restrict__ ent,
+                                                       int32_t *__restrict__ owner, float *__restrict__ dzf) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
+        ent[i] = n_ent;                                           // no entity: adds nothing
+        owner[i] = 0;
+        dzf[i] = 0.f;
+    }
+}
+
+// The positives of query d = blockIdx.x: wave w takes the CSR entries [i0 + 32 (w + 4 k), + 32), one per column of a
+// tile whose rows are all query d (filter_kernel's form).  Entries outside [0, N) are skipped.
+template <int KS, int SG>
+__global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char *__restrict__ qp, int B,
+                                                            const float *__restrict__ O, int N, int c, float dt,
+                                                            const int64_t *__restrict__ pair_slot,
+                                                            const int64_t *__restrict__ pair_ptr,
+                                                            const int64_t *__restrict__ pair_obj,
+                                                            double *__restrict__ rows_pos, float *__restrict__ dvpos,
+                                                            const int32_t *__restrict__ off, int64_t max_pos,
+                                                            int32_t *__restrict__ ent, int32_t *__restrict__ owner,
+                                                            float *__restrict__ dzf) {
+    __shared__ float part[BS_WAVES][256];
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int d = blockIdx.x;
+    const int64_t s = pair_slot[d];
+    const int64_t i0 = s >= 0 ? pair_ptr[s] : 0, i1 = s >= 0 ? pair_ptr[s + 1] : 0;
+    float lacc = 0.f;
+    float dva[4] = {0.f, 0.f, 0.f, 0.f};
+    if (i0 + 32 * wave < i1) {
+        const int mt = d >> 5, row = d & 31;
+        f16x8 A0[KS], A1[KS];
+        load_a<float, KS>(qp, mt, row, h, A0, A1);
+        const float srow = reinterpret_cast<const float *>(qp + mt * tile_bytes<float, KS>())[row];
+        Frag<float, KS> f;
+        for (int64_t base = i0 + 32 * wave; base < i1; base += 32 * BS_WAVES) {       // wave-uniform
+            const int64_t i = base + r;
+            const int64_t jr = i < i1 ? pair_obj[i] : -1;
+            const bool ok = jr >= 0 && jr < N;
+            float dz = 0.f;
+            if (__ballot(ok) != 0) {
+                f.load(O, ok ? jr : 0, c, h, true);
+                f.template convert<SG>();
+                const f32x16 acc = f.chain(A0, A1);
+                if (h == 0 && ok) {                                // element 0 of lane r: row 0, column r
+                    const float p = f.template prob<SG>(acc[0], srow);
+                    lacc += dt * (clog(p) - clog(1.0f - p));
+                    dz = (p == 1.0f || p == 0.0f) ? 0.f : -dt;
+                }
+            }
+            if (off && h == 0 && i < i1) {
+                const int64_t at = (int64_t)off[d] + (i - i0);
+                if (at < max_pos) {
+                    ent[at] = ok ? (int32_t)jr : N;
+                    owner[at] = d;
+                    dzf[at] = dz;
+                }
+            }
+            if (dvpos) {
+                for (int rr = 0; rr < 32; ++rr) {
+                    const float g = __shfl(dz, rr);
+                    const int j = __shfl((int)(ok ? jr : 0), rr);
+                    if (g != 0.f) {                                // (uniform)
+                        const float *oj = O + (int64_t)j * c;
+#pragma unroll
+                        for (int k = 0; k < 4; ++k)
+                            if (lane + 64 * k < c) dva[k] = fmaf(g, oj[lane + 64 * k], dva[k]);
+                    }
+                }
+            }
+        }
+    }
+    if (rows_pos) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) lacc += __shfl_xor(lacc, o);
+        if (lane == 0) rows_pos[(int64_t)d * BS_POS_Y + wave] = -(double)lacc;
+    }
+    if (dvpos) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) part[wave][lane + 64 * k] = dva[k];
+        __syncthreads();
+        const int col = threadIdx.x;
+        if (col < c) dvpos[(int64_t)d * c + col] = ((part[0][col] + part[1][col]) + part[2][col]) + part[3][col];
+    }
+}
+
+// vs = scale * v (the small operand of gO carries g / (B N))
+__global__ __launch_bounds__(256) void scale_v_kernel(const float *__restrict__ v, int64_t n, const float *__restrict__ scale,
+                                                      float *__restrict__ vs) {
+    const float s = scale[0];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) vs[i] = v[i] * s;
+}
+
+// the transposed images of vs, one per query tile, scaled by the power of two of its largest magnitude
+__global__ __launch_bounds__(256) void pack_v_kernel(const float *__restrict__ vs, int B, int c, int nct,
+                                                     const float *__restrict__ v_bound, _Float16 *__restrict__ vp) {
+    const int mt = blockIdx.x, cp = 32 * nct;
+    const float up = ldexpf(1.0f, rtk_pack_shift(v_bound[0]));
+    _Float16 *img = vp + (int64_t)mt * nct * 2048;
+    for (int i = threadIdx.x; i < 32 * cp; i += 256) {
+        const int j = i / cp, col = i - j * cp, d = mt * 32 + j;
+        const float y = (d < B && col < c) ? vs[(int64_t)d * c + col] * up : 0.f;
+        const _Float16 hi = (_Float16)y;
+        const int ix = timg_index(j, col);
+        img[ix] = hi;
+        img[nct * 1024 + ix] = (_Float16)(y - (float)hi);
+    }
+}
+
+template <int KS>
+struct GoLds {
+    static constexpr int TILE = (int)tile_bytes<float, KS>();      // the packed query tile (header + two planes)
+    static constexpr int BUF = TILE + timg_bytes(KS);              // ... and the tile's image of s v behind it
+    static constexpr int TOTAL = 2 * BUF;
+};
+
+// Sweep 2.  Workgroup w: entity tiles (128 rows) w, w + grid, ...; every query tile.
+template <int KS, int SG>
+__global__ __launch_bounds__(64 * BS_WAVES, 1) void go_kernel(const unsigned char *__restrict__ qp,
+                                                              const unsigned char *__restrict__ vp, int B,
+                                                              const float *__restrict__ O, int N, int c, float t0,
+                                                              const float *__restrict__ v_bound, float *__restrict__ gO) {
+    typedef GoLds<KS> L;
+    constexpr int NCT = nct_of(KS);
+    constexpr int NT = 64 * BS_WAVES;
+    constexpr int CH_Q = L::TILE / 16, CH = L::BUF / 16;
+    constexpr int NLD = (CH + NT - 1) / NT;
+    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
+
+    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
+    const int n_mt = (B + 31) >> 5, n_tiles = (N + 32 * BS_WAVES - 1) / (32 * BS_WAVES);
+    const float un = ldexpf(1.0f, -14 - rtk_pack_shift(v_bound[0]));
+
+    u32x4 stg[NLD];
+    auto stage_load = [&](int mt) {
+        const u32x4 *sq = reinterpret_cast<const u32x4 *>(qp + (int64_t)mt * L::TILE);
+        const u32x4 *sv = reinterpret_cast<const u32x4 *>(vp + (int64_t)mt * timg_bytes(KS));
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int ch = i * NT + t;
+            if (ch < CH_Q) stg[i] = sq[ch];
+            else if (ch < CH) stg[i] = sv[ch - CH_Q];
+        }
+    };
+    auto stage_store = [&](int buf) {
+        u32x4 *dst = reinterpret_cast<u32x4 *>(lds + buf * L::BUF);
+#pragma unroll
+        for (int i = 0; i < NLD; ++i) {
+            const int ch = i * NT + t;
+            if (ch < CH) dst[ch] = stg[i];
+        }
+    };
+
+    stage_load(0);
+    int it = 0;
+    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
+        const int j0 = tile * 32 * BS_WAVES + wave * 32;             // the wave's first row
+        Frag<float, KS> f;
+        f.load(O, min(j0 + r, N - 1), c, h, true);
+        f.template convert<SG>();
+        f32x16 gacc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) gacc[ct] = zero16();
+        if (tile == (int)blockIdx.x) {
+            stage_store(0);
+            __syncthreads();
+        }
+        for (int i = 0; i < n_mt; ++i, ++it) {
+            const int cur = it & 1;
+            const bool more = i + 1 < n_mt || tile + (int)gridDim.x < n_tiles;
+            if (more) stage_load(i + 1 < n_mt ? i + 1 : 0);
+            const unsigned char *buf = lds + cur * L::BUF;
+            const f16x8 *la = reinterpret_cast<const f16x8 *>(buf + RTK_PACK_HDR);
+            const f32x16 acc = f.chain_with([&](int plane, int ks) { return la[(plane * KS + ks) * 64 + lane]; });
+            // element e: query row 8 (e / 4) + 4 h + e % 4 of the tile, entity r of the wave
+            float x[16];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int rw = 8 * g + 4 * h;
+                const f32x4 sr4 = *reinterpret_cast<const f32x4 *>(buf + rw * 4);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const float p = f.template prob<SG>(acc[4 * g + q], sr4[q]);
+                    x[4 * g + q] = x_of(p, t0, i * 32 + rw + q < B);
+                }
+            }
+            f16x8 xh[2], xl[2];
+            split_x(x, xh, xl);
+            tile_product<NCT>(xh, xl, reinterpret_cast<const f16x8 *>(buf + L::TILE), lane, gacc);
+            if (more) stage_store(cur ^ 1);
+            __syncthreads();
+        }
+        // element e of gacc[ct]: entity row 8 (e / 4) + 4 h + e % 4 of the wave, column 32 ct + r; on top of the
+        // positives' share that the ordered scatter wrote
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            const int col = ct * 32 + r;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int j = j0 + 8 * (e >> 2) + 4 * h + (e & 3);
+                if (j < N && col < c) {
+                    float *dst = gO + (int64_t)j * c + col;
+                    *dst = gacc[ct][e] * un + *dst;
+                }
+            }
+        }
+    }
+}
+
+// ---- host side -------------------------------------------------------------------------------------------------
+
+int splits_of(int64_t batch) {
+    const int64_t n_qg = rtk_cdiv(rtk_cdiv(batch, 32), BS_WAVES);
+    const int64_t s = RTK_N_CU / (n_qg > 0 ? n_qg : 1);
+    return (int)(s < 1 ? 1 : s);
+}
+
+struct StreamWs {
+    size_t bounds, part_loss, rows_pos, slab, dvpos, vs, vp, off, ent, owner, dzf, sort, total;
+};
+StreamWs layout_of(int64_t batch, int c, int64_t max_pos) {
+    StreamWs L;
+    const int ks = (c + 15) / 16, nct = nct_of(ks);
+    const size_t B = (size_t)batch, S = (size_t)splits_of(batch), n_mt = (size_t)rtk_cdiv(batch, 32);
+    const size_t M = (size_t)(max_pos > 0 ? max_pos : 0);
+    size_t at = 256;                                          // [0, 256): the error word's header
+    auto take = [&](size_t bytes) {
+        const size_t p = at;
+        at += rtk_align_up(bytes, 256);
+        return p;
+    };
+    L.bounds = take(256);                                     // max |O|, max |s v|
+    L.part_loss = take(S * B * 8);
+    L.rows_pos = take(B * BS_POS_Y * 8);
+    L.slab = take(S * B * 32 * nct * 4);
+    L.dvpos = take(B * (size_t)c * 4);
+    L.vs = take(B * (size_t)c * 4);
+    L.vp = take(n_mt * (size_t)nct * 4096);
+    L.off = take((B + 1) * 4);
+    L.ent = take(M * 4);
+    L.owner = take(M * 4);
+    L.dzf = take(M * 4);
+    L.sort = take(rtk_cand_flat_workspace_bytes((int64_t)M));
+    L.total = at;
+    return L;
+}
+
+int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                 const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos, float eps,
+                 unsigned flags, const void *out, const void *workspace, size_t ws_bytes) {
+    RTK_REQUIRE(q_packed && O && pair_slot && pair_ptr && pair_obj && out && workspace, RTK_ERR_BAD_ARG, "%s: null operand",
+                fn);
+    RTK_REQUIRE(batch >= 0, RTK_ERR_BAD_ARG, "%s: batch = %lld must be >= 0", fn, (long long)batch);
+    RTK_REQUIRE(n_ent >= 1, RTK_ERR_BAD_ARG, "%s: n_ent = %lld must be >= 1", fn, (long long)n_ent);
+    RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
+    RTK_REQUIRE(c >= 1, RTK_ERR_BAD_ARG, "%s: object rank c = %d must be >= 1", fn, c);
+    RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
+    RTK_REQUIRE(batch < (1ll << 31) - 32 && n_ent < (1ll << 31) - 256 && max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED,
+                "%s: dimension too large", fn);
+    RTK_REQUIRE(flags & RTK_SCORE_SIGMOID, RTK_ERR_UNSUPPORTED,
+                "%s: the loss is taken on probabilities: flags need RTK_SCORE_SIGMOID", fn);
+    RTK_REQUIRE((flags & ~(RTK_SCORE_SIGMOID | RTK_SCORE_SIGMOID_FAST)) == 0, RTK_ERR_BAD_ARG, "%s: unknown flags 0x%x",
+                fn, flags);
+    RTK_REQUIRE(c <= 16 * BS_MAX_KS, RTK_ERR_UNSUPPORTED,
+                "%s: c = %d above %d (the matrix-free loss keeps a whole row of the accumulator in one wave)", fn, c,
+                16 * BS_MAX_KS);
+    RTK_REQUIRE(c % 4 == 0 && (reinterpret_cast<uintptr_t>(O) & 15) == 0, RTK_ERR_UNSUPPORTED,
+                "%s: fp32 needs c %% 4 == 0 and a 16-byte-aligned O (c = %d)", fn, c);
+    const size_t need = layout_of(batch, c, max_pos).total;
+    RTK_REQUIRE(ws_bytes >= need, RTK_ERR_BAD_ARG, "%s: workspace of %zu bytes given, %zu needed", fn, ws_bytes, need);
+    RTK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, RTK_ERR_BAD_ARG, "%s: workspace must be 256-byte aligned",
+                fn);
+    return RTK_OK;
+}
+
+template <int KS, int SG>
+int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, const int64_t *slot, const int64_t *ptr,
+                const int64_t *obj, float eps, double *loss_rows, float *dv, unsigned char *ws, const StreamWs &L,
+                hipStream_t st, const char *fn) {
+    const float t0 = eps / (float)N, dt = 1.0f - eps;
+    const int splits = splits_of(B), n_qg = (int)rtk_cdiv(rtk_cdiv(B, 32), BS_WAVES);
+    float *bounds = reinterpret_cast<float *>(ws + L.bounds);
+    double *part_loss = reinterpret_cast<double *>(ws + L.part_loss), *rows_pos = reinterpret_cast<double *>(ws + L.rows_pos);
+    float *slab = reinterpret_cast<float *>(ws + L.slab), *dvpos = reinterpret_cast<float *>(ws + L.dvpos);
+    if (dv) {
+        const int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
+        if (rc != RTK_OK) return rc;
+    }
+    hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, c, dt, slot, ptr, obj,
+                       rows_pos, dv ? dvpos : nullptr, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
+                       (int32_t *)nullptr, (float *)nullptr);
+    constexpr int bytes = RowsLds<KS>::TOTAL;
+    static_assert(bytes <= 64 * 1024, "rows_kernel: one 32-row tile in two layouts fits the default LDS limit");
+    const dim3 grid((unsigned)(n_qg * splits));
+    if (dv)
+        RTK_LAUNCH_SCORE((rows_kernel<KS, SG, true>), grid, dim3(64 * BS_WAVES), bytes, st, qp, B, O, N, c, t0, bounds, splits,
+                         part_loss, slab);
+    else
+        RTK_LAUNCH_SCORE((rows_kernel<KS, SG, false>), grid, dim3(64 * BS_WAVES), bytes, st, qp, B, O, N, c, t0, bounds, splits,
+                         part_loss, slab);
+    hipLaunchKernelGGL(rows_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, B, c, 32 * nct_of(KS), splits, part_loss,
+                       rows_pos, slab, dvpos, bounds, loss_rows, dv);
+    return RTK_OK;
+}
+
+template <int KS, int SG>
+int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, const int64_t *slot,
+                  const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps, const float *scale, float *gO,
+                  unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
+    const float t0 = eps / (float)N, dt = 1.0f - eps;
+    constexpr int NCT = nct_of(KS);
+    const int n_mt = (int)rtk_cdiv(B, 32);
+    uint32_t *err = reinterpret_cast<uint32_t *>(ws);
+    float *bounds = reinterpret_cast<float *>(ws + L.bounds), *vs = reinterpret_cast<float *>(ws + L.vs);
+    int32_t *off = reinterpret_cast<int32_t *>(ws + L.off), *ent = reinterpret_cast<int32_t *>(ws + L.ent);
+    int32_t *owner = reinterpret_cast<int32_t *>(ws + L.owner);
+    float *dzf = reinterpret_cast<float *>(ws + L.dzf);
+    const int64_t nv = (int64_t)B * c;
+    hipLaunchKernelGGL(scale_v_kernel, dim3((unsigned)(rtk_cdiv(nv, 256) < 1024 ? rtk_cdiv(nv, 256) : 1024)), dim3(256), 0, st,
+                       v, nv, scale, vs);
+    int rc = rtk_absmax_f32(vs, B, c, c, bounds + 1, (void *)st);
+    if (rc != RTK_OK) return rc;
+    hipLaunchKernelGGL(pack_v_kernel, dim3((unsigned)n_mt), dim3(256), 0, st, vs, B, c, NCT, bounds + 1,
+                       reinterpret_cast<_Float16 *>(ws + L.vp));
+    // the positives' share: flat lists, then the ordered scatter (which zeroes gO first)
+    if (max_pos > 0) {
+        hipLaunchKernelGGL(pos_fill_kernel, dim3((unsigned)(rtk_cdiv(max_pos, 256) < 1024 ? rtk_cdiv(max_pos, 256) : 1024)),
+                           dim3(256), 0, st, max_pos, (int32_t)N, ent, owner, dzf);
+        hipLaunchKernelGGL(pos_offsets_kernel, dim3(1), dim3(256), 0, st, B, slot, ptr, max_pos, off, err);
+        hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, c, dt, slot, ptr,
+                           obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
+    }
+    rc = rtk_cand_flat_scatter(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
+    if (rc != RTK_OK) return rc;
+    constexpr int bytes = GoLds<KS>::TOTAL;
+    static std::atomic<unsigned long long> lds_ok{0};
+    if (bytes > 64 * 1024) {
+        rc = rtk_ensure_dynamic_lds(reinterpret_cast<const void *>(&go_kernel<KS, SG>), bytes, lds_ok, fn);
+        if (rc != RTK_OK) return rc;
+    }
+    const int64_t n_tiles = rtk_cdiv(N, 32 * BS_WAVES);
+    RTK_LAUNCH_SCORE((go_kernel<KS, SG>), dim3((unsigned)(n_tiles < RTK_N_CU ? n_tiles : RTK_N_CU)), dim3(64 * BS_WAVES), bytes,
+                     st, qp, ws + L.vp, B, O, N, c, t0, bounds + 1, gO);
+    return RTK_OK;
+}
+
+}  // namespace
+
+extern "C" size_t rtk_bce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
+    if (batch < 0 || n_ent < 1 || c < 1 || c > 16 * BS_MAX_KS || max_pos < 0 || max_pos >= (1ll << 31) - 1) return 0;
+    return layout_of(batch, c, max_pos).total;
+}
+
+extern "C" int rtk_bce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                                       const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                                       float label_smoothing, unsigned flags, double *loss_rows_out, float *dv_out,
+                                       void *workspace, size_t ws_bytes, void *stream) {
+    const char *fn = "rtk_bce_stream_rows_f32";
+    int rc = check_stream(fn, q_packed, batch, c, O, n_ent, pair_slot, pair_ptr, pair_obj, 0, label_smoothing, flags,
+                          loss_rows_out, workspace, ws_bytes);
+    if (rc != RTK_OK || batch == 0) return rc;
+    const StreamWs L = layout_of(batch, c, 0);
+    const bool fast = (flags & RTK_SCORE_SIGMOID_FAST) != 0;
+    const unsigned char *qp = (const unsigned char *)q_packed;
+    unsigned char *ws = (unsigned char *)workspace;
+    hipStream_t st = (hipStream_t)stream;
+    rc = rtk_dispatch_ksteps<BS_MAX_KS>((c + 15) / 16, fn, [&](auto K) {
+        if (fast)
+            return launch_rows<K.value, 2>(qp, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, label_smoothing,
+                                           loss_rows_out, dv_out, ws, L, st, fn);
+        return launch_rows<K.value, 1>(qp, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, label_smoothing,
+                                       loss_rows_out, dv_out, ws, L, st, fn);
+    });
+    if (rc != RTK_OK) return rc;
+    return rtk_check_launch(fn);
+}
+
+extern "C" int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O,
+                                         int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                         const int64_t *pair_obj, int64_t max_pos, float label_smoothing, unsigned flags,
+                                         const float *scale, float *gO_out, void *workspace, size_t ws_bytes, void *stream) {
+    const char *fn = "rtk_bce_stream_grad_o_f32";
+    RTK_REQUIRE(v && scale, RTK_ERR_BAD_ARG, "%s: null operand", fn);
+    int rc = check_stream(fn, q_packed, batch, c, O, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, label_smoothing, flags,
+                          gO_out, workspace, ws_bytes);
+    if (rc != RTK_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (batch == 0) {                                         // no term touches any row
+        if (hipMemsetAsync(gO_out, 0, (size_t)n_ent * c * 4, st) != hipSuccess) {
+            rtk_set_error("%s: memset failed", fn);
+            return RTK_ERR_LAUNCH;
+        }
+        return RTK_OK;
+    }
+    const StreamWs L = layout_of(batch, c, max_pos);
+    const bool fast = (flags & RTK_SCORE_SIGMOID_FAST) != 0;
+    const unsigned char *qp = (const unsigned char *)q_packed;
+    unsigned char *ws = (unsigned char *)workspace;
+    rc = rtk_dispatch_ksteps<BS_MAX_KS>((c + 15) / 16, fn, [&](auto K) {
+        if (fast)
+            return launch_grad_o<K.value, 2>(qp, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, max_pos,
+                                             label_smoothing, scale, gO_out, ws, L, st, fn);
+        return launch_grad_o<K.value, 1>(qp, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, max_pos,
+                                         label_smoothing, scale, gO_out, ws, L, st, fn);
+    });
+    if (rc != RTK_OK) return rc;
+    return rtk_check_launch(fn);
+}

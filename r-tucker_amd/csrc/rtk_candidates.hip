@@ -357,7 +357,8 @@ template <int NCH, bool VEC>
 __global__ __launch_bounds__(256) void cand_go_kernel(const int32_t *__restrict__ skey, const int32_t *__restrict__ sval,
                                                      int64_t M, int64_t n_ent, const float *__restrict__ dz,
                                                      int64_t ld_dz, int64_t K, const float *__restrict__ v, int c,
-                                                     float *__restrict__ gO, float *__restrict__ P, int64_t win) {
+                                                     float *__restrict__ gO, float *__restrict__ P, int64_t win,
+                                                     const int32_t *__restrict__ owner) {
     constexpr int U = NCH <= 2 ? 8 : 4;
     const int lane = threadIdx.x & 63;
     const int64_t w = (int64_t)blockIdx.x * CAND_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -399,9 +400,11 @@ __global__ __launch_bounds__(256) void cand_go_kernel(const int32_t *__restrict_
         }
         u32x4 x[U][NCH];
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int u = 0; u < U; ++u) {
+            const int64_t vr = owner ? (int64_t)owner[dd[u]] : dd[u];      // flat list (K = 1): entry -> its query
 #pragma unroll
-            for (int i = 0; i < NCH; ++i) x[u][i] = load_piece<float, VEC>(v + dd[u] * c, i * 256 + lane * 4, c);
+            for (int i = 0; i < NCH; ++i) x[u][i] = load_piece<float, VEC>(v + vr * c, i * 256 + lane * 4, c);
+        }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             if (kk[u] < 0) break;
@@ -550,6 +553,53 @@ int score_candidates(const char *fn, const float *v, int64_t batch, int c, const
     return rtk_check_launch(fn);
 }
 
+// Flat front end of the ordered scatter (rtk_bce_stream.hip: the positives of a ragged CSR): M entries (entity ent[i],
+// query owner[i], logit gradient dz[i]); an entity outside [0, n_ent) adds nothing.  gO is zeroed, then written.
+__global__ __launch_bounds__(256) void flat_keys_kernel(const int32_t *__restrict__ ent, int64_t n_ent, int64_t M,
+                                                       int32_t *__restrict__ keys, int32_t *__restrict__ vals) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
+        const int32_t e = ent[i];
+        keys[i] = e >= 0 && e < n_ent ? e : (int32_t)n_ent;
+        vals[i] = (int32_t)i;
+    }
+}
+
+// The keys / vals of ws.keys[0], ws.vals[0] sorted by entity (stable), then the ordered sums into gO (zeroed by the caller).
+// `owner` (flat lists, k = 1): entry i belongs to query owner[i]; null: to query i / k.
+int sorted_scatter(const char *fn, const CandWs &ws, int64_t n_ent, const float *dz, int64_t ld_dz, int64_t k,
+                   const int32_t *owner, const float *v, int c, float *gO, hipStream_t st) {
+    const int64_t M = ws.M;
+    int bits = 1;
+    while ((n_ent >> bits) != 0) ++bits;             // keys are <= n_ent
+    const unsigned tblocks = (unsigned)rtk_cdiv(ws.ntiles, CAND_WAVES);
+    int src = 0;
+    for (int shift = 0; shift < bits; shift += 8, src ^= 1) {
+        hipLaunchKernelGGL(cand_hist_kernel, dim3(tblocks), dim3(256), 0, st, ws.keys[src], M, shift, ws.ntiles, ws.hist);
+        hipLaunchKernelGGL(scan_totals_kernel, dim3((unsigned)ws.nb), dim3(256), 0, st, ws.hist, ws.nh, ws.bs);
+        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, st, ws.bs, ws.nb);
+        hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)ws.nb), dim3(256), 0, st, ws.hist, ws.nh, ws.bs, ws.offs);
+        hipLaunchKernelGGL(cand_scatter_kernel, dim3(tblocks), dim3(256), 0, st, ws.keys[src], ws.vals[src], M, shift,
+                           ws.ntiles, ws.offs, ws.keys[src ^ 1], ws.vals[src ^ 1]);
+    }
+    const bool vec = c % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(gO)) & 15) == 0;
+    const unsigned wblocks = (unsigned)rtk_cdiv(ws.nwin, CAND_WAVES);
+    auto go = [&](auto nc, auto vc) {
+        constexpr int NC = decltype(nc)::value;
+        constexpr bool VC = decltype(vc)::value;
+        RTK_LAUNCH_SCORE((cand_go_kernel<NC, VC>), dim3(wblocks), dim3(256), 0, st, ws.keys[src], ws.vals[src], M, n_ent,
+                         dz, ld_dz, k, v, c, gO, ws.P, ws.win, owner);
+        hipLaunchKernelGGL((cand_go_combine_kernel<NC, VC>), dim3(wblocks), dim3(256), 0, st, ws.keys[src], M, n_ent, c, gO,
+                           ws.P, ws.win);
+    };
+    auto by_vec = [&](auto nc) { vec ? go(nc, std::true_type{}) : go(nc, std::false_type{}); };
+    const int nch = (c + 255) / 256;
+    if (nch == 1) by_vec(std::integral_constant<int, 1>{});
+    else if (nch == 2) by_vec(std::integral_constant<int, 2>{});
+    else if (nch == 3) by_vec(std::integral_constant<int, 3>{});
+    else by_vec(std::integral_constant<int, 4>{});
+    return rtk_check_launch(fn);
+}
+
 template <typename T>
 int score_candidates_bwd(const char *fn, const float *dz, int64_t ld_dz, const float *v, int64_t batch, int c, const T *O,
                          int64_t n_ent, const int64_t *cand, int64_t ld_cand, int64_t k, float *dv, float *gO,
@@ -603,38 +653,26 @@ int score_candidates_bwd(const char *fn, const float *dz, int64_t ld_dz, const f
     if (M == 0) return RTK_OK;
     const unsigned gblocks = (unsigned)(rtk_cdiv(M, 256) < 4096 ? rtk_cdiv(M, 256) : 4096);
     hipLaunchKernelGGL(cand_keys_kernel, dim3(gblocks), dim3(256), 0, st, cand, ld_cand, k, n_ent, M, ws.keys[0], ws.vals[0]);
-    int bits = 1;
-    while ((n_ent >> bits) != 0) ++bits;             // keys are <= n_ent
-    const unsigned tblocks = (unsigned)rtk_cdiv(ws.ntiles, CAND_WAVES);
-    int src = 0;
-    for (int shift = 0; shift < bits; shift += 8, src ^= 1) {
-        hipLaunchKernelGGL(cand_hist_kernel, dim3(tblocks), dim3(256), 0, st, ws.keys[src], M, shift, ws.ntiles, ws.hist);
-        hipLaunchKernelGGL(scan_totals_kernel, dim3((unsigned)ws.nb), dim3(256), 0, st, ws.hist, ws.nh, ws.bs);
-        hipLaunchKernelGGL(scan_blocks_kernel, dim3(1), dim3(256), 0, st, ws.bs, ws.nb);
-        hipLaunchKernelGGL(scan_final_kernel, dim3((unsigned)ws.nb), dim3(256), 0, st, ws.hist, ws.nh, ws.bs, ws.offs);
-        hipLaunchKernelGGL(cand_scatter_kernel, dim3(tblocks), dim3(256), 0, st, ws.keys[src], ws.vals[src], M, shift,
-                           ws.ntiles, ws.offs, ws.keys[src ^ 1], ws.vals[src ^ 1]);
-    }
-    const bool vec = c % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(gO)) & 15) == 0;
-    const unsigned wblocks = (unsigned)rtk_cdiv(ws.nwin, CAND_WAVES);
-    auto go = [&](auto nc, auto vc) {
-        constexpr int NC = decltype(nc)::value;
-        constexpr bool VC = decltype(vc)::value;
-        RTK_LAUNCH_SCORE((cand_go_kernel<NC, VC>), dim3(wblocks), dim3(256), 0, st, ws.keys[src], ws.vals[src], M, n_ent,
-                         dz, ld_dz, k, v, c, gO, ws.P, ws.win);
-        hipLaunchKernelGGL((cand_go_combine_kernel<NC, VC>), dim3(wblocks), dim3(256), 0, st, ws.keys[src], M, n_ent, c, gO,
-                           ws.P, ws.win);
-    };
-    auto by_vec = [&](auto nc) { vec ? go(nc, std::true_type{}) : go(nc, std::false_type{}); };
-    const int nch = (c + 255) / 256;
-    if (nch == 1) by_vec(std::integral_constant<int, 1>{});
-    else if (nch == 2) by_vec(std::integral_constant<int, 2>{});
-    else if (nch == 3) by_vec(std::integral_constant<int, 3>{});
-    else by_vec(std::integral_constant<int, 4>{});
-    return rtk_check_launch(fn);
+    return sorted_scatter(fn, ws, n_ent, dz, ld_dz, k, nullptr, v, c, gO, st);
 }
 
 }  // namespace
+
+size_t rtk_cand_flat_workspace_bytes(int64_t m) { return m <= 0 ? 0 : carve_cand(nullptr, m, 1).total; }
+
+int rtk_cand_flat_scatter(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m,
+                          int64_t n_ent, const float *v, int c, float *gO, void *workspace, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(gO, 0, (size_t)n_ent * c * 4, st);
+    if (e != hipSuccess) {
+        rtk_set_error("%s: memset: %s", fn, hipGetErrorString(e));
+        return RTK_ERR_LAUNCH;
+    }
+    if (m <= 0) return RTK_OK;
+    const CandWs ws = carve_cand(workspace, m, 1);
+    const unsigned gblocks = (unsigned)(rtk_cdiv(m, 256) < 4096 ? rtk_cdiv(m, 256) : 4096);
+    hipLaunchKernelGGL(flat_keys_kernel, dim3(gblocks), dim3(256), 0, st, ent, n_ent, m, ws.keys[0], ws.vals[0]);
+    return sorted_scatter(fn, ws, n_ent, dz, 1, 1, owner, v, c, gO, st);
+}
 
 extern "C" size_t rtk_score_candidates_bwd_workspace_bytes(int64_t batch, int64_t k, int64_t n_ent) {
     if (batch <= 0 || k <= 0 || n_ent <= 0 || batch >= (1ll << 31) || k >= (1ll << 31) || batch * k >= (1ll << 31)) return 0;

@@ -19,8 +19,14 @@
 
 namespace {
 
-// ln x on v_log_f32 (log2, 1 ulp); torch clamps BCE's logs at -100
-__device__ __forceinline__ float clog(float x) { return fmaxf(__builtin_amdgcn_logf(x) * 0.6931471805599453f, -100.0f); }
+// ln x on v_log_f32 (log2, 1 ulp), clamped at -100 like torch's BCE.  v_log_f32 reads a subnormal x as 0, and the exact logistic (an
+// IEEE division) does return subnormal probabilities (ln p between -87.3 and -103.3): those are scaled by 2^32 first.
+// A normal x gives the bits of the plain form.
+__device__ __forceinline__ float clog(float x) {
+    const bool sub = x < 1.17549435e-38f;
+    const float l2 = __builtin_amdgcn_logf(sub ? x * 4294967296.0f : x) - (sub ? 32.0f : 0.0f);
+    return fmaxf(l2 * 0.6931471805599453f, -100.0f);
+}
 
 // PARTIAL: target scores come from pt_in, the "+1" is left to the caller, ids are global
 template <bool PARTIAL>

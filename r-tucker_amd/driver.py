@@ -69,9 +69,12 @@ class RegularisedLoss:
         return self.data_term(T) + self.coeff * T.norm() ** 2
 
 
-def batch_loss_fn(model, subject_idx, relation_idx, flt, item_ids, label_smoothing, regularization_coeff):
+def batch_loss_fn(model, subject_idx, relation_idx, flt, item_ids, label_smoothing, regularization_coeff,
+                  matrix_free=False):
     """``loss_fn`` of ``train.py:79`` for one batch, as a function of the container ``T``.
-    ``regularization_coeff``: a float or a 0-dim device tensor (the captured step keeps it in device memory)."""
+    ``regularization_coeff``: a float or a 0-dim device tensor (the captured step keeps it in device memory).
+    ``matrix_free``: ``ops.bce_loss_1vN``'s form without the (B, N) matrix (object rank <= 208: not the Riemannian
+    step's doubled-rank construct)."""
     sym = _is_symmetric(model)
 
     def bce(T):
@@ -79,7 +82,8 @@ def batch_loss_fn(model, subject_idx, relation_idx, flt, item_ids, label_smoothi
             core, R, S, O = T.core, T.regular_factors[0], T.shared_factor, T.shared_factor
         else:
             core, (R, S, O) = T.core, T.factors
-        return ops.bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=label_smoothing)
+        return ops.bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=label_smoothing,
+                                matrix_free=matrix_free)
 
     return RegularisedLoss(bce, regularization_coeff)
 

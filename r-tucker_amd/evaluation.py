@@ -32,6 +32,7 @@ class DeviceFilter:
         m = int(obj.max()) + 1 if len(obj) else 1
         ptr = np.concatenate([[0], np.cumsum(np.bincount(key // m, minlength=len(ptr) - 1))]).astype(np.int64)
         obj = (key % m).astype(np.int64)
+        self.max_list = int(np.diff(ptr).max()) if len(ptr) > 1 else 0     # longest list (a host-known bound)
         self.pair_ptr = torch.as_tensor(ptr, device=self.device)
         self.pair_obj = torch.as_tensor(obj, device=self.device)
         f = np.asarray(dataset.features, dtype=np.int64)

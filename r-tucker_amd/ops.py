@@ -222,6 +222,9 @@ def _check_now(ws, sp):
         raise IndexError("index out of range in self (candidate id out of range)")
     if flag.value & 4:
         raise IndexError("index out of range in self (object_idx out of range)")
+    if flag.value & 8:
+        raise RuntimeError("bce_loss_1vN(matrix_free=True): the batch's queries list more known objects than max_pos "
+                           "(pass a larger max_pos)")
 
 
 def _strict_check(ws, sp):
@@ -579,16 +582,105 @@ class _BceLoss1vN(torch.autograd.Function):
         return _grads_from_dZ(core, R, S, O, h, r, v, P, ctx.needs_input_grad, pdt,
                               dz_bound=g.abs() * (1.0 / (B * N))) + (None,) * 6
 
+# Largest object rank of the matrix-free loss (rtk_bce_stream_*: one wave keeps a whole row of the dv / gO accumulator).
+_STREAM_MAX_C = 208
 
-def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0):
+
+class _BceLossStream(torch.autograd.Function):
+    """``_BceLoss1vN`` without the (B, N) matrix (``rtk_bce_stream_*``): sweep 1 (loss rows and dv) in the forward,
+    sweep 2 (gO) in the backward.  What is saved is of size B x c: the fp32 query vectors, their packed planes, dv."""
+
+    @staticmethod
+    def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, max_pos,
+                want_dv):
+        lib = _lib.load()
+        _require_gpu("core", core)
+        if core.dtype != torch.float32:
+            raise RuntimeError(f"bce_loss_1vN(matrix_free=True): float32 operands only, got {core.dtype} "
+                               "(bf16 operands stay on the matrix form)")
+        op = _Operands(core, R, S, O, subject_idx, relation_idx)
+        B, N, c, dev = op.B, op.O.shape[0], op.c, op.dev
+        if c > _STREAM_MAX_C or c % 4 != 0 or op.O.data_ptr() % 16 != 0:
+            raise RuntimeError(f"bce_loss_1vN(matrix_free=True): object rank c = {c} outside the matrix-free range "
+                               f"(c <= {_STREAM_MAX_C}, c % 4 == 0, 16-byte-aligned O); use matrix_free=False")
+        ctx.flags = flags = _score_flags(True, sigmoid_mode, torch.float32, False)
+        ctx.eps, ctx.max_pos, ctx.B = float(eps), int(max_pos), B
+        if B == 0:
+            ctx.save_for_backward(op.core, op.R, op.S, op.O)
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        v = torch.empty((B, c), dtype=torch.float32, device=dev)
+        qp = torch.empty(_size("rtk_packed_query_bytes", op.dcode, B, c), dtype=torch.uint8, device=dev)
+        rows = torch.empty(B, dtype=torch.float64, device=dev)
+        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            _strict_check(_stage1(op, sp, None, v, qp), sp)
+            ws = _workspace(dev, sp, _size("rtk_bce_stream_workspace_bytes", B, N, c, 0))
+            _lib.check(lib.rtk_bce_stream_rows_f32(qp.data_ptr(), B, c, op.O.data_ptr(), N, pair_slot.data_ptr(),
+                                                   pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, flags, rows.data_ptr(),
+                                                   dv.data_ptr() if want_dv else None, ws.data_ptr(), ws.numel(), sp),
+                       "rtk_bce_stream_rows_f32")
+        ctx.has_dv = want_dv
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, qp, pair_slot, pair_ptr, pair_obj,
+                              *((dv,) if want_dv else ()))
+        return (rows.sum() / (B * N)).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        needs = ctx.needs_input_grad
+        if ctx.B == 0:
+            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 9
+        core, R, S, O, h, r, v, qp, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors[:11]
+        lib = _lib.load()
+        dev = v.device
+        B, c = v.shape
+        N = O.shape[0]
+        g = (grad_loss.to(device=dev, dtype=torch.float32).reshape(1) * (1.0 / (B * N))).contiguous()
+        gcore = gR = gS = gO = None
+        if needs[3]:
+            gO = torch.empty((N, c), dtype=torch.float32, device=dev)
+            with torch.cuda.device(dev):
+                sp = _stream_ptr(dev)
+                ws = _workspace(dev, sp, _size("rtk_bce_stream_workspace_bytes", B, N, c, ctx.max_pos))
+                _lib.check(lib.rtk_bce_stream_grad_o_f32(qp.data_ptr(), v.data_ptr(), B, c, O.data_ptr(), N,
+                                                         pair_slot.data_ptr(), pair_ptr.data_ptr(), pair_obj.data_ptr(),
+                                                         ctx.max_pos, ctx.eps, ctx.flags, g.data_ptr(), gO.data_ptr(),
+                                                         ws.data_ptr(), ws.numel(), sp), "rtk_bce_stream_grad_o_f32")
+                _strict_check(ws, sp)
+        if any(needs[:3]):
+            if not ctx.has_dv:
+                raise RuntimeError("bce_loss_1vN(matrix_free=True): dv was not computed in the forward")
+            gcore, gR, gS = _stage1_backward(core, R, S, h, r, ctx.saved_tensors[11] * g, needs)
+        # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
+        return (gcore, gR, gS, gO) + (None,) * 9
+
+
+def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, matrix_free=False,
+                 sigmoid_mode=None, max_pos=None):
     """The reference's training loss term ``nn.BCELoss()(score_fn(T), targets)`` (train.py:79,136) for a
     batch of (subject, relation) items WITHOUT the dense target matrix: ``flt`` is the
     ``evaluation.DeviceFilter`` of the train-mode ``KG_dataset`` (CSR of known objects per pair, on
     the device), ``item_ids`` the dataset indices of the batch; the targets
     ``(1 - eps) * multi_hot + eps / N`` (Dataset.py:51-52) are applied inside the kernels.
-    Differentiable w.r.t. core and factors like ``score_1vN``."""
+    Differentiable w.r.t. core and factors like ``score_1vN``.
+
+    ``matrix_free=True``: the same loss and gradients without the (B, N) matrix (``rtk_bce_stream_*``): nothing that
+    grows with B x N is allocated in forward, backward or between them.  float32 operands with ``c <= 208``,
+    ``c % 4 == 0`` (anything else raises; there is no fallback).  ``sigmoid_mode`` ("fast" / "exact", default
+    ``DEFAULT_SIGMOID``) applies to this form only; the probabilities are the ws score kernel's.  ``max_pos``: an upper
+    bound on the number of CSR entries of the batch's queries (default ``B * flt.max_list``, which always holds)."""
     dev = core.device
     slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
+    if matrix_free:
+        if max_pos is None:
+            mx = getattr(flt, "max_list", None)
+            max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+        # dv (the second tile product of sweep 1) only when a gradient of core, R or S can be asked for
+        want_dv = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S))
+        return _BceLossStream.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
+                                    float(label_smoothing), sigmoid_mode, int(max_pos), want_dv)
+    if sigmoid_mode is not None or max_pos is not None:
+        raise ValueError("sigmoid_mode and max_pos belong to matrix_free=True")
     return _BceLoss1vN.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                              float(label_smoothing))
 

@@ -18,7 +18,8 @@ import r_tucker_amd as rt  # noqa: E402
 from r_tucker_amd.data import Data, KG_dataset  # noqa: E402
 
 
-def train(epochs=30, rank=(10, 200, 200), batch=512, lr=3e-3, seed=322, smoothing=0.1, log=print, lr_decay=1.0):
+def train(epochs=30, rank=(10, 200, 200), batch=512, lr=3e-3, seed=322, smoothing=0.1, log=print, lr_decay=1.0,
+          matrix_free=False):
     torch.manual_seed(seed)
     np.random.seed(seed)
     data = Data(os.path.join(ROOT, "data", "WN18RR") + "/", reverse=True)
@@ -42,7 +43,8 @@ def train(epochs=30, rank=(10, 200, 200), batch=512, lr=3e-3, seed=322, smoothin
             f = flt.features[ids]
             opt.zero_grad(set_to_none=True)
             loss = rt.bce_loss_1vN(model.core, model.R.weight, model.S.weight, model.O.weight,
-                                   f[:, 0].contiguous(), f[:, 1].contiguous(), flt, ids, label_smoothing=smoothing)
+                                   f[:, 0].contiguous(), f[:, 1].contiguous(), flt, ids, label_smoothing=smoothing,
+                                   matrix_free=matrix_free)
             loss.backward()
             opt.step()
             tot += float(loss.detach()) if (lo // batch) % 50 == 0 else 0.0
@@ -59,5 +61,6 @@ if __name__ == "__main__":
     ap.add_argument("--epochs", type=int, default=30)
     ap.add_argument("--lr", type=float, default=3e-3)
     ap.add_argument("--lr-decay", type=float, default=1.0)
+    ap.add_argument("--matrix-free", action="store_true", help="the loss without the (B, N) score matrix")
     a = ap.parse_args()
-    train(a.epochs, lr=a.lr, lr_decay=a.lr_decay)
+    train(a.epochs, lr=a.lr, lr_decay=a.lr_decay, matrix_free=a.matrix_free)
