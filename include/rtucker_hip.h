@@ -674,6 +674,46 @@ int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, int64_t batc
                               const int64_t *pair_obj, int64_t max_pos, float label_smoothing, unsigned flags,
                               const float *scale, float *gO_out, void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * The same two sweeps on one block of entity rows (an entity shard): the caller holds rows [col0, col0 + n_local) of the
+ * (n_ent x c) entity matrix as O_local; pair_obj holds GLOBAL entity ids (the conventions of rtk_score_rank_targets_* /
+ * rtk_score_rank_counts_*).  The loss and dv are sums over entities and a row of gO belongs to the block that owns it:
+ *   rtk_bce_stream_rows_part_f32    loss_rows_out[d] = the block's share of sum_j BCE(p[d, j], y[d, j]), j over the
+ *                                   block's rows only; dv_out[d, :] = sum_{j in block} x[d, j] O[j, :] (unscaled; NULL:
+ *                                   not computed).  All-reduce SUM over the ranks completes both (batch doubles in the
+ *                                   forward, batch x c floats in the backward, before rtk_query_vectors_bwd_f32).
+ *   rtk_bce_stream_grad_o_part_f32  gO_local_out (n_local x c) = the block's rows of gO, written in full; no exchange.
+ * Summed (rows, dv) or concatenated (gO) over any partition of [0, n_ent) into blocks they are the outputs of
+ * rtk_bce_stream_rows_f32 / rtk_bce_stream_grad_o_f32 on the whole matrix up to the order of the fp32 / fp64 sums;
+ * with col0 = 0 and n_local = n_ent they have those calls' bits (the whole-matrix entry points ARE this block).
+ * The smoothing term is eps / n_ent, the GLOBAL entity count, and the caller's scale is g / (batch n_ent).  A CSR
+ * entry e belongs to the block iff col0 <= e < col0 + n_local (local row e - col0); the others are skipped in the loss
+ * correction, in the positives' share of dv and in the ordered scatter's lists (they keep their slot with the "adds
+ * nothing" key, so the launch sequence depends on batch, c, n_local and max_pos only: static, graph-capturable).
+ * max_pos bounds the CSR entries of the batch's queries in ALL blocks, as for the whole matrix.  The O-wide power of
+ * two of sweep 1's second product comes from the block's own rows.  Element arithmetic, summation orders within the
+ * block, determinism, flags, covered range and refusals as rtk_bce_stream_*; in addition col0 < 0, n_local < 1 or
+ * col0 + n_local > n_ent give RTK_ERR_BAD_ARG before anything is enqueued.  batch == 0: rows returns at once, grad_o
+ * zeroes gO_local_out.
+ * Workspace: rtk_bce_stream_part_workspace_bytes(batch, n_local, c, max_pos), valid without a device, 256-byte
+ * aligned, first word the error word; the formula of rtk_bce_stream_workspace_bytes,
+ *     512 + align256(8 S batch) + align256(32 batch) + align256(4 S batch cp) + 2 align256(4 batch c)
+ *         + align256(128 cp ceil(batch / 32)) + align256(4 (batch + 1)) + 3 align256(4 max_pos)
+ *         + rtk_score_candidates_bwd_workspace_bytes(max_pos, 1, .),
+ * cp = 32 * ceil(c / 32), S = max(1, 256 / ceil(batch / 128)): n_local does not enter, nothing grows with
+ * batch * n_local.
+ */
+size_t rtk_bce_stream_part_workspace_bytes(int64_t batch, int64_t n_local, int c, int64_t max_pos);
+int rtk_bce_stream_rows_part_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                                 int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                 const int64_t *pair_obj, float label_smoothing, unsigned flags,
+                                 double *loss_rows_out, float *dv_out, void *workspace, size_t ws_bytes, void *stream);
+int rtk_bce_stream_grad_o_part_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O_local,
+                                   int64_t n_local, int64_t col0, int64_t n_ent, const int64_t *pair_slot,
+                                   const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos,
+                                   float label_smoothing, unsigned flags, const float *scale, float *gO_local_out,
+                                   void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

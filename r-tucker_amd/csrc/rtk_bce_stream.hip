@@ -22,6 +22,11 @@
 //                 gives the loss correction -(1 - eps) (ln p - ln(1 - p)), the positives' share of dv, and the flat
 //                 (entity, query, dz) lists that the ordered scatter of rtk_candidates.hip turns into their share of gO.
 //
+// The block form (rtk_bce_stream_*_part_f32): O holds rows [col0, col0 + N) of an n_ent-row matrix.  The sweeps are
+// row-local, so they only take the smoothing term eps / n_ent from the host; pos_kernel owns the CSR entries whose
+// GLOBAL id falls into the block and works on local rows.  The whole-matrix entry points are the block launchers with
+// col0 = 0, N = n_ent.
+//
 // Both tile products are three f16 MFMAs per k-step on hi/lo halves (x scaled by 2^14; O and s v by a power of two from
 // their largest magnitude), accumulated in fp32.  No float atomics: every sum has a fixed order.
 #include "rtk_common.h"
@@ -318,10 +323,11 @@ __global__ __launch_bounds__(256) void pos_fill_kernel(int64_t m, int32_t n_ent,
 }
 
 // The positives of query d = blockIdx.x: wave w takes the CSR entries [i0 + 32 (w + 4 k), + 32), one per column of a
-// tile whose rows are all query d (filter_kernel's form).  Entries outside [0, N) are skipped.
+// tile whose rows are all query d (filter_kernel's form).  pair_obj holds global ids; the block owns col0 <= id < col0 + N
+// (local row id - col0), every other entry is skipped.
 template <int KS, int SG>
 __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char *__restrict__ qp, int B,
-                                                            const float *__restrict__ O, int N, int c, float dt,
+                                                            const float *__restrict__ O, int N, int col0, int c, float dt,
                                                             const int64_t *__restrict__ pair_slot,
                                                             const int64_t *__restrict__ pair_ptr,
                                                             const int64_t *__restrict__ pair_obj,
@@ -345,7 +351,7 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
         Frag<float, KS> f;
         for (int64_t base = i0 + 32 * wave; base < i1; base += 32 * BS_WAVES) {       // wave-uniform
             const int64_t i = base + r;
-            const int64_t jr = i < i1 ? pair_obj[i] : -1;
+            const int64_t jr = i < i1 ? pair_obj[i] - col0 : -1;     // local row
             const bool ok = jr >= 0 && jr < N;
             float dz = 0.f;
             if (__ballot(ok) != 0) {
@@ -555,13 +561,16 @@ StreamWs layout_of(int64_t batch, int c, int64_t max_pos) {
     return L;
 }
 
-int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
-                 const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos, float eps,
+int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, const float *O, int64_t n_local, int64_t col0,
+                 int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos, float eps,
                  unsigned flags, const void *out, const void *workspace, size_t ws_bytes) {
     RTK_REQUIRE(q_packed && O && pair_slot && pair_ptr && pair_obj && out && workspace, RTK_ERR_BAD_ARG, "%s: null operand",
                 fn);
     RTK_REQUIRE(batch >= 0, RTK_ERR_BAD_ARG, "%s: batch = %lld must be >= 0", fn, (long long)batch);
     RTK_REQUIRE(n_ent >= 1, RTK_ERR_BAD_ARG, "%s: n_ent = %lld must be >= 1", fn, (long long)n_ent);
+    RTK_REQUIRE(col0 >= 0 && n_local >= 1 && n_local <= n_ent && col0 <= n_ent - n_local, RTK_ERR_BAD_ARG,
+                "%s: block [col0 = %lld, + n_local = %lld) is not a non-empty part of [0, n_ent = %lld)", fn, (long long)col0,
+                (long long)n_local, (long long)n_ent);
     RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
     RTK_REQUIRE(c >= 1, RTK_ERR_BAD_ARG, "%s: object rank c = %d must be >= 1", fn, c);
     RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
@@ -584,10 +593,10 @@ int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, con
 }
 
 template <int KS, int SG>
-int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, const int64_t *slot, const int64_t *ptr,
-                const int64_t *obj, float eps, double *loss_rows, float *dv, unsigned char *ws, const StreamWs &L,
-                hipStream_t st, const char *fn) {
-    const float t0 = eps / (float)N, dt = 1.0f - eps;
+int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, int col0, int n_ent, const int64_t *slot,
+                const int64_t *ptr, const int64_t *obj, float eps, double *loss_rows, float *dv, unsigned char *ws,
+                const StreamWs &L, hipStream_t st, const char *fn) {
+    const float t0 = eps / (float)n_ent, dt = 1.0f - eps;       // the smoothing term of the WHOLE entity count
     const int splits = splits_of(B), n_qg = (int)rtk_cdiv(rtk_cdiv(B, 32), BS_WAVES);
     float *bounds = reinterpret_cast<float *>(ws + L.bounds);
     double *part_loss = reinterpret_cast<double *>(ws + L.part_loss), *rows_pos = reinterpret_cast<double *>(ws + L.rows_pos);
@@ -596,8 +605,8 @@ int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, co
         const int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
         if (rc != RTK_OK) return rc;
     }
-    hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, c, dt, slot, ptr, obj,
-                       rows_pos, dv ? dvpos : nullptr, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
+    hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot, ptr,
+                       obj, rows_pos, dv ? dvpos : nullptr, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
                        (int32_t *)nullptr, (float *)nullptr);
     constexpr int bytes = RowsLds<KS>::TOTAL;
     static_assert(bytes <= 64 * 1024, "rows_kernel: one 32-row tile in two layouts fits the default LDS limit");
@@ -614,10 +623,10 @@ int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, co
 }
 
 template <int KS, int SG>
-int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, const int64_t *slot,
-                  const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps, const float *scale, float *gO,
-                  unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
-    const float t0 = eps / (float)N, dt = 1.0f - eps;
+int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, int n_ent,
+                  const int64_t *slot, const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps,
+                  const float *scale, float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
+    const float t0 = eps / (float)n_ent, dt = 1.0f - eps;
     constexpr int NCT = nct_of(KS);
     const int n_mt = (int)rtk_cdiv(B, 32);
     uint32_t *err = reinterpret_cast<uint32_t *>(ws);
@@ -637,8 +646,8 @@ int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const f
         hipLaunchKernelGGL(pos_fill_kernel, dim3((unsigned)(rtk_cdiv(max_pos, 256) < 1024 ? rtk_cdiv(max_pos, 256) : 1024)),
                            dim3(256), 0, st, max_pos, (int32_t)N, ent, owner, dzf);
         hipLaunchKernelGGL(pos_offsets_kernel, dim3(1), dim3(256), 0, st, B, slot, ptr, max_pos, off, err);
-        hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, c, dt, slot, ptr,
-                           obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
+        hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot,
+                           ptr, obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
     }
     rc = rtk_cand_flat_scatter(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
     if (rc != RTK_OK) return rc;
@@ -654,19 +663,11 @@ int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const f
     return RTK_OK;
 }
 
-}  // namespace
-
-extern "C" size_t rtk_bce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
-    if (batch < 0 || n_ent < 1 || c < 1 || c > 16 * BS_MAX_KS || max_pos < 0 || max_pos >= (1ll << 31) - 1) return 0;
-    return layout_of(batch, c, max_pos).total;
-}
-
-extern "C" int rtk_bce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
-                                       const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
-                                       float label_smoothing, unsigned flags, double *loss_rows_out, float *dv_out,
-                                       void *workspace, size_t ws_bytes, void *stream) {
-    const char *fn = "rtk_bce_stream_rows_f32";
-    int rc = check_stream(fn, q_packed, batch, c, O, n_ent, pair_slot, pair_ptr, pair_obj, 0, label_smoothing, flags,
+// The two sweeps on rows [col0, col0 + n_local) of the (n_ent x c) matrix; the whole matrix is the block (0, n_ent).
+int stream_rows(const char *fn, const void *q_packed, int64_t batch, int c, const float *O, int64_t n_local, int64_t col0,
+                int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj, float eps,
+                unsigned flags, double *loss_rows_out, float *dv_out, void *workspace, size_t ws_bytes, void *stream) {
+    int rc = check_stream(fn, q_packed, batch, c, O, n_local, col0, n_ent, pair_slot, pair_ptr, pair_obj, 0, eps, flags,
                           loss_rows_out, workspace, ws_bytes);
     if (rc != RTK_OK || batch == 0) return rc;
     const StreamWs L = layout_of(batch, c, 0);
@@ -676,27 +677,26 @@ extern "C" int rtk_bce_stream_rows_f32(const void *q_packed, int64_t batch, int 
     hipStream_t st = (hipStream_t)stream;
     rc = rtk_dispatch_ksteps<BS_MAX_KS>((c + 15) / 16, fn, [&](auto K) {
         if (fast)
-            return launch_rows<K.value, 2>(qp, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, label_smoothing,
-                                           loss_rows_out, dv_out, ws, L, st, fn);
-        return launch_rows<K.value, 1>(qp, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, label_smoothing,
-                                       loss_rows_out, dv_out, ws, L, st, fn);
+            return launch_rows<K.value, 2>(qp, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
+                                           pair_obj, eps, loss_rows_out, dv_out, ws, L, st, fn);
+        return launch_rows<K.value, 1>(qp, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
+                                       pair_obj, eps, loss_rows_out, dv_out, ws, L, st, fn);
     });
     if (rc != RTK_OK) return rc;
     return rtk_check_launch(fn);
 }
 
-extern "C" int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O,
-                                         int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
-                                         const int64_t *pair_obj, int64_t max_pos, float label_smoothing, unsigned flags,
-                                         const float *scale, float *gO_out, void *workspace, size_t ws_bytes, void *stream) {
-    const char *fn = "rtk_bce_stream_grad_o_f32";
+int stream_grad_o(const char *fn, const void *q_packed, const float *v, int64_t batch, int c, const float *O, int64_t n_local,
+                  int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                  int64_t max_pos, float eps, unsigned flags, const float *scale, float *gO_out, void *workspace,
+                  size_t ws_bytes, void *stream) {
     RTK_REQUIRE(v && scale, RTK_ERR_BAD_ARG, "%s: null operand", fn);
-    int rc = check_stream(fn, q_packed, batch, c, O, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, label_smoothing, flags,
+    int rc = check_stream(fn, q_packed, batch, c, O, n_local, col0, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps, flags,
                           gO_out, workspace, ws_bytes);
     if (rc != RTK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (batch == 0) {                                         // no term touches any row
-        if (hipMemsetAsync(gO_out, 0, (size_t)n_ent * c * 4, st) != hipSuccess) {
+        if (hipMemsetAsync(gO_out, 0, (size_t)n_local * c * 4, st) != hipSuccess) {
             rtk_set_error("%s: memset failed", fn);
             return RTK_ERR_LAUNCH;
         }
@@ -708,11 +708,56 @@ extern "C" int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, i
     unsigned char *ws = (unsigned char *)workspace;
     rc = rtk_dispatch_ksteps<BS_MAX_KS>((c + 15) / 16, fn, [&](auto K) {
         if (fast)
-            return launch_grad_o<K.value, 2>(qp, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, max_pos,
-                                             label_smoothing, scale, gO_out, ws, L, st, fn);
-        return launch_grad_o<K.value, 1>(qp, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj, max_pos,
-                                         label_smoothing, scale, gO_out, ws, L, st, fn);
+            return launch_grad_o<K.value, 2>(qp, v, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
+                                             pair_obj, max_pos, eps, scale, gO_out, ws, L, st, fn);
+        return launch_grad_o<K.value, 1>(qp, v, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
+                                         pair_obj, max_pos, eps, scale, gO_out, ws, L, st, fn);
     });
     if (rc != RTK_OK) return rc;
     return rtk_check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" size_t rtk_bce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
+    if (batch < 0 || n_ent < 1 || c < 1 || c > 16 * BS_MAX_KS || max_pos < 0 || max_pos >= (1ll << 31) - 1) return 0;
+    return layout_of(batch, c, max_pos).total;
+}
+
+extern "C" size_t rtk_bce_stream_part_workspace_bytes(int64_t batch, int64_t n_local, int c, int64_t max_pos) {
+    return rtk_bce_stream_workspace_bytes(batch, n_local, c, max_pos);
+}
+
+extern "C" int rtk_bce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                                       const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                                       float label_smoothing, unsigned flags, double *loss_rows_out, float *dv_out,
+                                       void *workspace, size_t ws_bytes, void *stream) {
+    return stream_rows("rtk_bce_stream_rows_f32", q_packed, batch, c, O, n_ent, 0, n_ent, pair_slot, pair_ptr, pair_obj,
+                       label_smoothing, flags, loss_rows_out, dv_out, workspace, ws_bytes, stream);
+}
+
+extern "C" int rtk_bce_stream_rows_part_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                                            int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                            const int64_t *pair_obj, float label_smoothing, unsigned flags,
+                                            double *loss_rows_out, float *dv_out, void *workspace, size_t ws_bytes,
+                                            void *stream) {
+    return stream_rows("rtk_bce_stream_rows_part_f32", q_packed, batch, c, O_local, n_local, col0, n_ent, pair_slot, pair_ptr,
+                       pair_obj, label_smoothing, flags, loss_rows_out, dv_out, workspace, ws_bytes, stream);
+}
+
+extern "C" int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O,
+                                         int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                         const int64_t *pair_obj, int64_t max_pos, float label_smoothing, unsigned flags,
+                                         const float *scale, float *gO_out, void *workspace, size_t ws_bytes, void *stream) {
+    return stream_grad_o("rtk_bce_stream_grad_o_f32", q_packed, v, batch, c, O, n_ent, 0, n_ent, pair_slot, pair_ptr, pair_obj,
+                         max_pos, label_smoothing, flags, scale, gO_out, workspace, ws_bytes, stream);
+}
+
+extern "C" int rtk_bce_stream_grad_o_part_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O_local,
+                                              int64_t n_local, int64_t col0, int64_t n_ent, const int64_t *pair_slot,
+                                              const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos,
+                                              float label_smoothing, unsigned flags, const float *scale, float *gO_local_out,
+                                              void *workspace, size_t ws_bytes, void *stream) {
+    return stream_grad_o("rtk_bce_stream_grad_o_part_f32", q_packed, v, batch, c, O_local, n_local, col0, n_ent, pair_slot,
+                         pair_ptr, pair_obj, max_pos, label_smoothing, flags, scale, gO_local_out, workspace, ws_bytes, stream);
 }

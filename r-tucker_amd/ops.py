@@ -685,6 +685,169 @@ def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_
                              float(label_smoothing))
 
 
+class _HipBlockLoss:
+    """The device steps of the block loss (``rtk_bce_stream_*_part_f32`` around stage 1 and its backward).
+    ``ShardedEntityScorer.bce_loss_1vN`` lets tests put CPU functions with these signatures in their place."""
+
+    @staticmethod
+    def operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent):
+        """The checked, contiguous operands ``(core, R, S, O_loc, h, r)``; the refusals of ``matrix_free=True``."""
+        _require_gpu("core", core)
+        if core.dtype != torch.float32:
+            raise RuntimeError(f"bce_loss_block_1vN: float32 operands only, got {core.dtype} "
+                               "(bf16 operands stay on the matrix form)")
+        op = _Operands(core, R, S, O_loc, subject_idx, relation_idx)
+        n_local, c = op.O.shape
+        if c > _STREAM_MAX_C or c % 4 != 0 or op.O.data_ptr() % 16 != 0:
+            raise RuntimeError(f"bce_loss_block_1vN: object rank c = {c} outside the matrix-free range "
+                               f"(c <= {_STREAM_MAX_C}, c % 4 == 0, 16-byte-aligned O_loc)")
+        if col0 < 0 or n_ent < 1 or col0 + n_local > n_ent:
+            raise RuntimeError(f"bce_loss_block_1vN: block [{col0}, {col0} + {n_local}) is not a part of "
+                               f"[0, n_ent = {n_ent})")
+        return op.core, op.R, op.S, op.O, op.h, op.r
+
+    @staticmethod
+    def queries(core, R, S, h, r):
+        """Stage 1 of all B queries: the fp32 query vectors and their packed planes."""
+        op = _Operands(core, R, S, None, h, r)
+        v = torch.empty((op.B, op.c), dtype=torch.float32, device=op.dev)
+        qp = torch.empty(_size("rtk_packed_query_bytes", op.dcode, op.B, op.c), dtype=torch.uint8, device=op.dev)
+        with torch.cuda.device(op.dev):
+            sp = _stream_ptr(op.dev)
+            _strict_check(_stage1(op, sp, None, v, qp), sp)
+        return v, qp
+
+    @staticmethod
+    def rows(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, want_dv):
+        """Sweep 1 on the block: ``(rows float64 (B,), dv float32 (B, c) or None)``, the block's shares."""
+        lib = _lib.load()
+        dev = O_loc.device
+        n_local, c = O_loc.shape
+        flags = _score_flags(True, sigmoid_mode, torch.float32, False)
+        rows = torch.empty(B, dtype=torch.float64, device=dev)
+        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_bce_stream_part_workspace_bytes", B, n_local, c, 0))
+            _lib.check(lib.rtk_bce_stream_rows_part_f32(qp.data_ptr(), B, c, O_loc.data_ptr(), n_local, col0, n_ent,
+                                                        pair_slot.data_ptr(), pair_ptr.data_ptr(), pair_obj.data_ptr(),
+                                                        eps, flags, rows.data_ptr(), dv.data_ptr() if want_dv else None,
+                                                        ws.data_ptr(), ws.numel(), sp), "rtk_bce_stream_rows_part_f32")
+        return rows, dv
+
+    @staticmethod
+    def grad_o(qp, v, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps, sigmoid_mode, scale):
+        """Sweep 2 on the block: its rows of gO, ``scale`` (one float on the device) = g / (B n_ent)."""
+        lib = _lib.load()
+        dev = O_loc.device
+        n_local, c = O_loc.shape
+        flags = _score_flags(True, sigmoid_mode, torch.float32, False)
+        gO = torch.empty((n_local, c), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_bce_stream_part_workspace_bytes", B, n_local, c, max_pos))
+            _lib.check(lib.rtk_bce_stream_grad_o_part_f32(qp.data_ptr(), v.data_ptr(), B, c, O_loc.data_ptr(), n_local, col0,
+                                                          n_ent, pair_slot.data_ptr(), pair_ptr.data_ptr(),
+                                                          pair_obj.data_ptr(), max_pos, eps, flags, scale.data_ptr(),
+                                                          gO.data_ptr(), ws.data_ptr(), ws.numel(), sp),
+                       "rtk_bce_stream_grad_o_part_f32")
+            _strict_check(ws, sp)
+        return gO
+
+    @staticmethod
+    def stage1_backward(core, R, S, h, r, dv, needs):
+        """``(g_core, g_R, g_S)`` from the scaled dv."""
+        return _stage1_backward(core, R, S, h, r, dv, needs)
+
+
+class _BceLossBlock(torch.autograd.Function):
+    """``_BceLossStream`` on rows ``[col0, col0 + n_local)`` of the entity matrix.  Without ``all_reduce`` the block's
+    share of the loss and of the gradients of core, R, S; with it the loss rows are summed over the ranks in the forward
+    and dv in the backward, before the (linear) stage-1 backward.  The gradient of ``O_loc`` is always local."""
+
+    @staticmethod
+    def forward(ctx, core, R, S, O_loc, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, max_pos,
+                want_dv, col0, n_ent, all_reduce, steps):
+        core, R, S, O_loc, h, r = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent)
+        B, (n_local, c), dev = h.numel(), O_loc.shape, core.device
+        # float32 like _BceLossStream; float64 stand-ins of the steps (tests on the CPU) keep their precision
+        ctx.ldt = ldt = torch.float64 if core.dtype == torch.float64 else torch.float32
+        ctx.eps, ctx.max_pos, ctx.B, ctx.mode = float(eps), int(max_pos), B, sigmoid_mode
+        ctx.col0, ctx.n_ent, ctx.all_reduce, ctx.steps, ctx.has_dv = col0, n_ent, all_reduce, steps, want_dv
+        if B == 0:
+            ctx.save_for_backward(core, R, S, O_loc)
+            return torch.zeros((), dtype=ldt, device=dev)
+        v = qp = None
+        if n_local > 0:
+            v, qp = steps.queries(core, R, S, h, r)
+            rows, dv = steps.rows(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, ctx.eps, sigmoid_mode, want_dv)
+        else:                                    # a rank without rows adds nothing and still takes part in the sums
+            rows = torch.zeros(B, dtype=torch.float64, device=dev)
+            dv = torch.zeros((B, c), dtype=ldt, device=dev) if want_dv else None
+        if all_reduce is not None:
+            all_reduce(rows)
+        ctx.save_for_backward(core, R, S, O_loc, h, r, v, qp, pair_slot, pair_ptr, pair_obj, dv)
+        return (rows.sum() / (B * n_ent)).to(ldt)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        needs = ctx.needs_input_grad
+        if ctx.B == 0:
+            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 13
+        core, R, S, O_loc, h, r, v, qp, pair_slot, pair_ptr, pair_obj, dv = ctx.saved_tensors
+        steps, B, dev = ctx.steps, ctx.B, core.device
+        g = (grad_loss.to(device=dev, dtype=ctx.ldt).reshape(1) * (1.0 / (B * ctx.n_ent))).contiguous()
+        gcore = gR = gS = gO = None
+        if needs[3]:
+            gO = (steps.grad_o(qp, v, B, O_loc, ctx.col0, ctx.n_ent, pair_slot, pair_ptr, pair_obj, ctx.max_pos, ctx.eps,
+                               ctx.mode, g) if O_loc.shape[0] > 0 else torch.zeros_like(O_loc))
+        if any(needs[:3]):
+            if not ctx.has_dv:
+                raise RuntimeError("bce_loss_block_1vN: dv was not computed in the forward")
+            if ctx.all_reduce is not None:       # dv, (B, c), never gS, (n_ent, b); the saved share stays as it is
+                dv = dv.clone()
+                ctx.all_reduce(dv)
+            gcore, gR, gS = steps.stage1_backward(core, R, S, h, r, dv * g, needs)
+        return (gcore, gR, gS, gO) + (None,) * 13
+
+
+def _block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing,
+                sigmoid_mode, max_pos, all_reduce):
+    dev = core.device
+    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
+    if max_pos is None:
+        mx = getattr(flt, "max_list", None)
+        max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+    want_dv = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S))
+    return _BceLossBlock.apply(core, R, S, O_loc, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
+                               float(label_smoothing), sigmoid_mode, int(max_pos), want_dv, int(col0), int(n_ent),
+                               all_reduce, steps)
+
+
+def bce_loss_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0,
+                       sigmoid_mode=None, max_pos=None, all_reduce=None):
+    """``bce_loss_1vN(..., matrix_free=True)`` on one block of entity rows (an entity shard), without anything of size
+    B x n_local (``rtk_bce_stream_rows_part_f32`` / ``rtk_bce_stream_grad_o_part_f32``).  ``O_loc``: rows
+    ``[col0, col0 + n_local)`` of the (n_ent, c) entity matrix; ``flt`` holds GLOBAL entity ids; the smoothing term is
+    ``eps / n_ent``.  S is only indexed by ``subject_idx`` and need not have n_ent rows.
+
+    ``all_reduce=None``: the block's SHARE of the loss, ``rows.sum() / (B * n_ent)``; its backward gives the block's
+    share of the gradients of core, R and S (the stage-1 backward is linear in dv) and the gradient of ``O_loc``.
+    Summed over any partition of [0, n_ent) the shares are the loss and gradients of the whole matrix.
+
+    ``all_reduce=fn`` (``fn(t)`` sums ``t`` in place over the ranks): the forward reduces the B float64 loss rows and
+    returns the complete loss, equal on every rank; the backward reduces dv (B x c floats) before the stage-1
+    backward, so core / R / S receive their complete gradients, identical on every rank -- do not average them again;
+    ``O_loc.grad`` is local.  A block without rows contributes zeros and still calls ``fn``.
+
+    float32, ``c <= 208``, ``c % 4 == 0`` (anything else raises; no fallback); ``sigmoid_mode`` / ``max_pos`` / the
+    ``index_check`` policy as ``bce_loss_1vN(matrix_free=True)``; ``max_pos`` bounds the CSR entries of the batch's
+    queries in all blocks.  Under ``no_grad``, or when core, R and S want no gradient, dv is not computed."""
+    _require_gpu("core", core)
+    return _block_loss(_HipBlockLoss, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids,
+                       label_smoothing, sigmoid_mode, max_pos, all_reduce)
+
+
 def score_1vN(core, R, S, O, subject_idx, relation_idx, sigmoid=True, exact=False, sigmoid_mode=None,
               out_dtype=torch.float32, tables=None):
     """``sigmoid((G x_0 R[r] x_1 S[h]) . O^T)`` for a batch of (h, r) queries -> ``(B, N)``.

@@ -327,6 +327,49 @@ class ShardedEntityScorer:
         ranks = counts + 1
         return (ranks, bce) if want_bce else ranks
 
+    # ---- the training loss without the gather and without the score block ----------------------
+    def bce_loss_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0,
+                     sigmoid_mode=None, max_pos=None, rows_fn=None, grad_o_fn=None, stage1_bwd_fn=None):
+        """The 1-vs-all BCE training loss with the entity matrix row-sharded and nothing of size B x n_loc allocated
+        (``ops.bce_loss_block_1vN`` on this rank's REAL rows, ``col0 = rank * n_loc``; ``flt`` holds global entity
+        ids).  The loss is a sum over entities: the forward completes the B float64 loss rows with one
+        all-reduce(SUM) and returns the whole loss, equal on every rank.  The backward completes dv (B x c floats)
+        with one all-reduce(SUM) before the stage-1 backward, so ``core.grad``, ``R.grad`` and ``S.grad`` are complete
+        and identical on every rank (do not average them again); ``O_loc.grad`` is this rank's rows of the gradient
+        of O and needs no exchange.  The last shard's zero padding rows are not entities: they add neither loss nor
+        smoothing terms and their gradient is 0.  A rank without rows contributes zeros and still takes part in both
+        all-reduces.  Without a process group (world size 1) this is ``ops.bce_loss_1vN(..., matrix_free=True)`` bit
+        for bit.
+
+        Stage 1 and its backward stay replicated: every rank computes all B query vectors from the replicated core,
+        R and S (the scorer's ``stage1`` policy does not apply here).
+
+        ``rows_fn`` / ``grad_o_fn`` / ``stage1_bwd_fn`` take the arguments of ``ops._HipBlockLoss.rows`` / ``grad_o``
+        / ``stage1_backward``; tests inject CPU functions (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
+        from . import ops
+        n_ent, n_loc = self.shards.n_ent, self.shards.n_loc
+        lo = min(self.rank * n_loc, n_ent)
+        n_valid = max(0, min(n_loc, n_ent - lo))                 # the last shard's padding rows are not entities
+        steps = ops._HipBlockLoss
+        if rows_fn or grad_o_fn or stage1_bwd_fn or self.query_vectors_fn is not None:
+            from types import SimpleNamespace
+
+            def queries(core_, R_, S_, h, r):
+                v = self.query_vectors_fn(core_, R_, S_, h, r)
+                return v, (self.pack_fn or ops.pack_query_vectors)(v, O_loc.dtype)
+
+            steps = SimpleNamespace(
+                operands=lambda c_, R_, S_, O_, h, r, col0, n: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
+                queries=queries if self.query_vectors_fn is not None else steps.queries,
+                rows=rows_fn or steps.rows, grad_o=grad_o_fn or steps.grad_o,
+                stage1_backward=stage1_bwd_fn or steps.stage1_backward)
+        reduce = None
+        if self.world > 1:
+            def reduce(t):
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+        return ops._block_loss(steps, core, R, S, O_loc[:n_valid], lo, n_ent, subject_idx, relation_idx, flt, item_ids,
+                               label_smoothing, sigmoid_mode, max_pos, reduce)
+
     # ---- top-k without the gather ----------------------------------------------------------
     def topk(self, core, R, S, O_loc, subject_idx, relation_idx, k, flt=None, slots=None, keep_idx=None,
              local_topk_fn=None, merge_fn=None, **kw):

@@ -19,7 +19,11 @@ from r_tucker_amd.data import Data, KG_dataset  # noqa: E402
 
 
 def train(epochs=30, rank=(10, 200, 200), batch=512, lr=3e-3, seed=322, smoothing=0.1, log=print, lr_decay=1.0,
-          matrix_free=False):
+          matrix_free=False, shards=1):
+    """``shards`` > 1 (with ``matrix_free``): the loss as the sum of the shares of P emulated entity blocks on this one
+    GPU (``bce_loss_block_1vN``, ``all_reduce=None``): what P ranks compute, without the two all-reduces."""
+    if shards > 1 and not matrix_free:
+        raise ValueError("--shards needs --matrix-free (the block form exists for the matrix-free loss only)")
     torch.manual_seed(seed)
     np.random.seed(seed)
     data = Data(os.path.join(ROOT, "data", "WN18RR") + "/", reverse=True)
@@ -42,9 +46,15 @@ def train(epochs=30, rank=(10, 200, 200), batch=512, lr=3e-3, seed=322, smoothin
             ids = perm[lo:lo + batch]
             f = flt.features[ids]
             opt.zero_grad(set_to_none=True)
-            loss = rt.bce_loss_1vN(model.core, model.R.weight, model.S.weight, model.O.weight,
-                                   f[:, 0].contiguous(), f[:, 1].contiguous(), flt, ids, label_smoothing=smoothing,
-                                   matrix_free=matrix_free)
+            if shards > 1:
+                cuts = [n_ent * k // shards for k in range(shards + 1)]
+                loss = sum(rt.bce_loss_block_1vN(model.core, model.R.weight, model.S.weight, model.O.weight[b0:b1], b0, n_ent,
+                                                 f[:, 0].contiguous(), f[:, 1].contiguous(), flt, ids,
+                                                 label_smoothing=smoothing) for b0, b1 in zip(cuts, cuts[1:]))
+            else:
+                loss = rt.bce_loss_1vN(model.core, model.R.weight, model.S.weight, model.O.weight,
+                                       f[:, 0].contiguous(), f[:, 1].contiguous(), flt, ids, label_smoothing=smoothing,
+                                       matrix_free=matrix_free)
             loss.backward()
             opt.step()
             tot += float(loss.detach()) if (lo // batch) % 50 == 0 else 0.0
@@ -62,5 +72,6 @@ if __name__ == "__main__":
     ap.add_argument("--lr", type=float, default=3e-3)
     ap.add_argument("--lr-decay", type=float, default=1.0)
     ap.add_argument("--matrix-free", action="store_true", help="the loss without the (B, N) score matrix")
+    ap.add_argument("--shards", type=int, default=1, help="with --matrix-free: P emulated entity blocks, shares summed")
     a = ap.parse_args()
-    train(a.epochs, lr=a.lr, lr_decay=a.lr_decay, matrix_free=a.matrix_free)
+    train(a.epochs, lr=a.lr, lr_decay=a.lr_decay, matrix_free=a.matrix_free, shards=a.shards)
