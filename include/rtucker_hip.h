@@ -540,7 +540,10 @@ int rtk_bce_grad_f32(float *P, int64_t batch, int64_t n_ent, int64_t ld, const i
                      const float *grad_loss, float scale, void *stream);
 
 /*
- * Filtered ranks without the (batch x n_ent) score matrix (rtk_score_rank.hip).  For query d with object t = obj_idx[d]
+ * Filtered ranks without the (batch x n_ent) score matrix (rtk_score_rank.hip): the one-block call of the block form
+ * below (col0 = 0, n_local = n_ent), on the caller's stream target_kernel (p_t of every query, kept in the workspace),
+ * count_kernel, filter_kernel (only with pair_slot) and finish_kernel, which writes 1 + count.  For query d with object
+ * t = obj_idx[d]
  *   rank[d] = 1 + #{ j : p'_j > p_t } + #{ j < t : p'_j == p_t }
  * on probabilities (the logistic RTK_SCORE_SIGMOID selects, with or without RTK_SCORE_SIGMOID_FAST; raw logits are not
  * ranked: flags without RTK_SCORE_SIGMOID give RTK_ERR_UNSUPPORTED), where p' is p with the query's other known-true
@@ -548,10 +551,14 @@ int rtk_bce_grad_f32(float *P, int64_t batch, int64_t n_ent, int64_t ld, const i
  * rtk_filtered_rank_f32.  NaN never counts.  CSR entries outside [0, n_ent) are skipped.  pair_slot may be NULL.
  *   q_packed   packed query planes of the batch (stage 1, as for rtk_score_packed_*)
  *   bce_rows   NULL, or per-row BCE sums as rtk_filtered_rank_f32 returns them (every CSR object positive, logs
- *              clamped at -100); summation order differs, so they agree to ~1e-6 relative.  Reduced in a fixed
- *              order (no float atomics): repeated calls give the same bits.
- *   workspace  rtk_score_rank_workspace_bytes (valid without a device), 256-byte aligned; its first word is the
- *              error word (the workspace of the stage 1 that made q_packed serves, once large enough).
+ *              clamped at -100); summation order differs, so they agree to ~1e-6 relative.  Reduced in the block
+ *              form's fixed order (float partials per workgroup slot and query tile, added in slot order in float64;
+ *              no float atomics): repeated calls give the same bits.
+ *   workspace  rtk_score_rank_workspace_bytes (valid without a device), 256-byte aligned:
+ *                  rtk_score_rank_part_workspace_bytes(dtype, batch, n_ent, c) + align256(4 * batch)
+ *              -- the block layout at n_local = n_ent and the batch's p_t behind it (34.1 MB at batch 8192,
+ *              n_ent 1 000 000; the query-stationary kernels this call ran on before needed 1.1 MB there).  Its first
+ *              word is the error word (the workspace of the stage 1 that made q_packed serves, once large enough).
  * Exactness: each probability is computed with the element arithmetic of the stored kernels, so
  *   _f32:  ranks equal rtk_filtered_rank_f32 over the scores of rtk_score_packed_f32 with RTK_SCORE_KERNEL_WS and the
  *          same flags.  The default fp32 dispatch differs from those scores only on the column-group kernel's fifth-group
@@ -576,7 +583,7 @@ int rtk_score_rank_bf16(const void *q_packed, int64_t batch, int c, const void *
 
 /*
  * The same ranking on one block of entity rows (an entity shard), without the (batch x n_local) score block
- * (rtk_score_rank_part.hip): the matrix-free twins of rtk_target_scores_f32 / rtk_filtered_rank_partial_f32.  The
+ * (rtk_score_rank.hip): the matrix-free twins of rtk_target_scores_f32 / rtk_filtered_rank_partial_f32.  The
  * caller holds rows [col0, col0 + n_local) of the (n_ent x c) entity matrix as O_local; obj_idx and pair_obj hold
  * GLOBAL entity ids.
  *   1. rtk_score_rank_targets_*: pt_out[d] = probability of (query d, obj_idx[d]) where the block owns the object
@@ -587,11 +594,12 @@ int rtk_score_rank_bf16(const void *q_packed, int64_t batch, int c, const void *
  *      rtk_score_rank_* (the query's other CSR objects count as probability 0, the queried object is never
  *      counted, NaN never counts, CSR entries outside the block are ignored; the CSR lists each object once);
  *      bce_rows_out (optional): its share of the row's BCE sum.  All-reduce SUM, then rank = 1 + count.
- * Element arithmetic is that of rtk_score_rank_* (one shared implementation), so for every partition of [0, n_ent)
- * into blocks 1 + the sum of the blocks' counts EQUALS the ranks of rtk_score_rank_* on the whole range, in both
- * logistic modes, and pt after the MAX has the bits of that call's internal target score.  The BCE shares sum to
- * its bce_rows to ~1e-6 relative; they are reduced in a fixed order (no float atomics): repeated calls give the
- * same bits.
+ * rtk_score_rank_* IS the one-block call (these two steps at col0 = 0, n_local = n_ent, the finish pass adding the
+ * 1), so for one block 1 + counts equals its ranks by construction; for every other partition of [0, n_ent) into
+ * blocks 1 + the sum of the blocks' counts EQUALS them too, in both logistic modes, because every probability has the
+ * same bits in every block and integer counts add exactly.  pt after the MAX has the bits of that call's internal
+ * target score.  The BCE shares sum to its bce_rows to ~1e-6 relative; they are reduced in a fixed order (no float
+ * atomics): repeated calls give the same bits.
  * The dense pass of step 2 is entity-stationary: every row of O_local is converted into MFMA operands once per
  * call (once per query range when n_local < 65 536), not once per 32-query tile.
  * Workspace: rtk_score_rank_part_workspace_bytes (valid without a device), 256-byte aligned, for both steps:

@@ -14,7 +14,7 @@
 //                 (the chain's operand with the per-row scaling of Frag, and the k-permuted transposed operand of the
 //                 dv product with one scale for all of O).  The BCE terms of the tile are summed per query.  The entity
 //                 range is cut into `splits` parts; slabs and loss partials are added by finish_kernel in split order.
-//   go_kernel     sweep 2, count_kernel's skeleton (rtk_score_rank_part.hip): a wave converts its 32 entity rows once,
+//   go_kernel     sweep 2, count_kernel's skeleton (rtk_score_rank.hip): a wave converts its 32 entity rows once,
 //                 sweeps the query tiles staged through LDS together with the packed tile of s v, and accumulates
 //                 gO[j, :] += sum_d x[d, j] (s v[d, :]).  Here the entity is on the lane and the tile is the A operand
 //                 of X^T V.  A wave owns its 32 rows of gO: one read-add-store on top of the positives' share.

@@ -1,7 +1,8 @@
-// Operand fragments of the matrix-free ranking kernels (rtk_score_rank.hip, rtk_score_rank_part.hip; internal header):
-// the B fragments of one entity row, their conversion, the MFMA chain against the packed query planes and the logistic.
-// Both files take every probability from here, so a (query row, entity row, c) triple has the same bits in the
-// query-stationary sweep, in the entity-stationary counting kernel and in the per-query passes.
+// Operand fragments of the matrix-free ranking and loss kernels (rtk_score_rank.hip, rtk_bce_stream.hip; internal
+// header): the B fragments of one entity row, their conversion, the MFMA chain against the packed query planes and the
+// logistic.  Both files take every probability from here, so a (query row, entity row, c) triple has the same bits in
+// the entity-stationary kernels (count_kernel, the loss sweeps) and in the per-query passes (target_kernel,
+// filter_kernel).
 #pragma once
 #include "rtk_common.h"
 #include "rtk_pack.h"

@@ -446,16 +446,7 @@ def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, pdt, dz_bound=None, scale=
                                                    splits, skw.data_ptr(), skw.numel(), sp), "rtk_gemm_f32_splitk (dv)")
             if scale is not None:
                 dv = dv * scale.to(device=dev, dtype=torch.float32).reshape(1)
-            gcore = torch.empty_like(core) if needs[0] else None
-            gR = torch.empty_like(R) if needs[1] else None
-            gS = torch.empty_like(S) if needs[2] else None
-            bws = torch.empty(lib.rtk_query_bwd_workspace_bytes(B, a, b, c), dtype=torch.uint8, device=dev)
-            _lib.check(lib.rtk_query_vectors_bwd_f32(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0], S.data_ptr(),
-                                                     S.shape[0], r.data_ptr(), h.data_ptr(), B, dv.data_ptr(),
-                                                     gcore.data_ptr() if needs[0] else None,
-                                                     gR.data_ptr() if needs[1] else None,
-                                                     gS.data_ptr() if needs[2] else None,
-                                                     bws.data_ptr(), bws.numel(), sp), "rtk_query_vectors_bwd_f32")
+            gcore, gR, gS = _stage1_backward(core, R, S, h, r, dv, needs)
     if pdt != torch.float32:
         gcore, gR, gS, gO = [g.to(pdt) if g is not None else None for g in (gcore, gR, gS, gO)]
     # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
@@ -586,75 +577,6 @@ class _BceLoss1vN(torch.autograd.Function):
 _STREAM_MAX_C = 208
 
 
-class _BceLossStream(torch.autograd.Function):
-    """``_BceLoss1vN`` without the (B, N) matrix (``rtk_bce_stream_*``): sweep 1 (loss rows and dv) in the forward,
-    sweep 2 (gO) in the backward.  What is saved is of size B x c: the fp32 query vectors, their packed planes, dv."""
-
-    @staticmethod
-    def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, max_pos,
-                want_dv):
-        lib = _lib.load()
-        _require_gpu("core", core)
-        if core.dtype != torch.float32:
-            raise RuntimeError(f"bce_loss_1vN(matrix_free=True): float32 operands only, got {core.dtype} "
-                               "(bf16 operands stay on the matrix form)")
-        op = _Operands(core, R, S, O, subject_idx, relation_idx)
-        B, N, c, dev = op.B, op.O.shape[0], op.c, op.dev
-        if c > _STREAM_MAX_C or c % 4 != 0 or op.O.data_ptr() % 16 != 0:
-            raise RuntimeError(f"bce_loss_1vN(matrix_free=True): object rank c = {c} outside the matrix-free range "
-                               f"(c <= {_STREAM_MAX_C}, c % 4 == 0, 16-byte-aligned O); use matrix_free=False")
-        ctx.flags = flags = _score_flags(True, sigmoid_mode, torch.float32, False)
-        ctx.eps, ctx.max_pos, ctx.B = float(eps), int(max_pos), B
-        if B == 0:
-            ctx.save_for_backward(op.core, op.R, op.S, op.O)
-            return torch.zeros((), dtype=torch.float32, device=dev)
-        v = torch.empty((B, c), dtype=torch.float32, device=dev)
-        qp = torch.empty(_size("rtk_packed_query_bytes", op.dcode, B, c), dtype=torch.uint8, device=dev)
-        rows = torch.empty(B, dtype=torch.float64, device=dev)
-        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
-        with torch.cuda.device(dev):
-            sp = _stream_ptr(dev)
-            _strict_check(_stage1(op, sp, None, v, qp), sp)
-            ws = _workspace(dev, sp, _size("rtk_bce_stream_workspace_bytes", B, N, c, 0))
-            _lib.check(lib.rtk_bce_stream_rows_f32(qp.data_ptr(), B, c, op.O.data_ptr(), N, pair_slot.data_ptr(),
-                                                   pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, flags, rows.data_ptr(),
-                                                   dv.data_ptr() if want_dv else None, ws.data_ptr(), ws.numel(), sp),
-                       "rtk_bce_stream_rows_f32")
-        ctx.has_dv = want_dv
-        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, qp, pair_slot, pair_ptr, pair_obj,
-                              *((dv,) if want_dv else ()))
-        return (rows.sum() / (B * N)).to(torch.float32)
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        needs = ctx.needs_input_grad
-        if ctx.B == 0:
-            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 9
-        core, R, S, O, h, r, v, qp, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors[:11]
-        lib = _lib.load()
-        dev = v.device
-        B, c = v.shape
-        N = O.shape[0]
-        g = (grad_loss.to(device=dev, dtype=torch.float32).reshape(1) * (1.0 / (B * N))).contiguous()
-        gcore = gR = gS = gO = None
-        if needs[3]:
-            gO = torch.empty((N, c), dtype=torch.float32, device=dev)
-            with torch.cuda.device(dev):
-                sp = _stream_ptr(dev)
-                ws = _workspace(dev, sp, _size("rtk_bce_stream_workspace_bytes", B, N, c, ctx.max_pos))
-                _lib.check(lib.rtk_bce_stream_grad_o_f32(qp.data_ptr(), v.data_ptr(), B, c, O.data_ptr(), N,
-                                                         pair_slot.data_ptr(), pair_ptr.data_ptr(), pair_obj.data_ptr(),
-                                                         ctx.max_pos, ctx.eps, ctx.flags, g.data_ptr(), gO.data_ptr(),
-                                                         ws.data_ptr(), ws.numel(), sp), "rtk_bce_stream_grad_o_f32")
-                _strict_check(ws, sp)
-        if any(needs[:3]):
-            if not ctx.has_dv:
-                raise RuntimeError("bce_loss_1vN(matrix_free=True): dv was not computed in the forward")
-            gcore, gR, gS = _stage1_backward(core, R, S, h, r, ctx.saved_tensors[11] * g, needs)
-        # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
-        return (gcore, gR, gS, gO) + (None,) * 9
-
-
 def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, matrix_free=False,
                  sigmoid_mode=None, max_pos=None):
     """The reference's training loss term ``nn.BCELoss()(score_fn(T), targets)`` (train.py:79,136) for a
@@ -669,18 +591,12 @@ def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_
     ``c % 4 == 0`` (anything else raises; there is no fallback).  ``sigmoid_mode`` ("fast" / "exact", default
     ``DEFAULT_SIGMOID``) applies to this form only; the probabilities are the ws score kernel's.  ``max_pos``: an upper
     bound on the number of CSR entries of the batch's queries (default ``B * flt.max_list``, which always holds)."""
-    dev = core.device
-    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-    if matrix_free:
-        if max_pos is None:
-            mx = getattr(flt, "max_list", None)
-            max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
-        # dv (the second tile product of sweep 1) only when a gradient of core, R or S can be asked for
-        want_dv = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S))
-        return _BceLossStream.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
-                                    float(label_smoothing), sigmoid_mode, int(max_pos), want_dv)
+    if matrix_free:                      # the whole matrix is one block: col0 = 0, n_ent = N, nothing to reduce
+        return _block_loss(_HipBlockLoss, core, R, S, O, 0, O.shape[0], subject_idx, relation_idx, flt, item_ids,
+                           label_smoothing, sigmoid_mode, max_pos, None, who="bce_loss_1vN(matrix_free=True)")
     if sigmoid_mode is not None or max_pos is not None:
         raise ValueError("sigmoid_mode and max_pos belong to matrix_free=True")
+    slot = flt.slot_of_item[item_ids.to(core.device)].contiguous()
     return _BceLoss1vN.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                              float(label_smoothing))
 
@@ -690,20 +606,19 @@ class _HipBlockLoss:
     ``ShardedEntityScorer.bce_loss_1vN`` lets tests put CPU functions with these signatures in their place."""
 
     @staticmethod
-    def operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent):
-        """The checked, contiguous operands ``(core, R, S, O_loc, h, r)``; the refusals of ``matrix_free=True``."""
+    def operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who):
+        """The checked, contiguous operands ``(core, R, S, O_loc, h, r)``; the refusals of ``matrix_free=True``, under
+        the name ``who`` of the public function that was called."""
         _require_gpu("core", core)
         if core.dtype != torch.float32:
-            raise RuntimeError(f"bce_loss_block_1vN: float32 operands only, got {core.dtype} "
-                               "(bf16 operands stay on the matrix form)")
+            raise RuntimeError(f"{who}: float32 operands only, got {core.dtype} (bf16 operands stay on the matrix form)")
         op = _Operands(core, R, S, O_loc, subject_idx, relation_idx)
         n_local, c = op.O.shape
         if c > _STREAM_MAX_C or c % 4 != 0 or op.O.data_ptr() % 16 != 0:
-            raise RuntimeError(f"bce_loss_block_1vN: object rank c = {c} outside the matrix-free range "
-                               f"(c <= {_STREAM_MAX_C}, c % 4 == 0, 16-byte-aligned O_loc)")
+            raise RuntimeError(f"{who}: object rank c = {c} outside the matrix-free range "
+                               f"(c <= {_STREAM_MAX_C}, c % 4 == 0, 16-byte-aligned O)")
         if col0 < 0 or n_ent < 1 or col0 + n_local > n_ent:
-            raise RuntimeError(f"bce_loss_block_1vN: block [{col0}, {col0} + {n_local}) is not a part of "
-                               f"[0, n_ent = {n_ent})")
+            raise RuntimeError(f"{who}: block [{col0}, {col0} + {n_local}) is not a part of [0, n_ent = {n_ent})")
         return op.core, op.R, op.S, op.O, op.h, op.r
 
     @staticmethod
@@ -761,18 +676,21 @@ class _HipBlockLoss:
 
 
 class _BceLossBlock(torch.autograd.Function):
-    """``_BceLossStream`` on rows ``[col0, col0 + n_local)`` of the entity matrix.  Without ``all_reduce`` the block's
-    share of the loss and of the gradients of core, R, S; with it the loss rows are summed over the ranks in the forward
-    and dv in the backward, before the (linear) stage-1 backward.  The gradient of ``O_loc`` is always local."""
+    """``_BceLoss1vN`` without the score matrix (``rtk_bce_stream_*_part_f32``), on rows ``[col0, col0 + n_local)`` of the
+    entity matrix: sweep 1 (loss rows and dv) in the forward, sweep 2 (gO) in the backward.  What is saved is of size
+    B x c: the fp32 query vectors, their packed planes, dv.  The whole matrix is the block ``col0 = 0, n_ent = N``.
+    Without ``all_reduce`` the block's share of the loss and of the gradients of core, R, S; with it the loss rows are
+    summed over the ranks in the forward and dv in the backward, before the (linear) stage-1 backward.  The gradient of
+    ``O_loc`` is always local.  ``who``: the public function's name, for the refusals."""
 
     @staticmethod
     def forward(ctx, core, R, S, O_loc, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, max_pos,
-                want_dv, col0, n_ent, all_reduce, steps):
-        core, R, S, O_loc, h, r = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent)
+                want_dv, col0, n_ent, all_reduce, steps, who="bce_loss_block_1vN"):
+        core, R, S, O_loc, h, r = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who)
         B, (n_local, c), dev = h.numel(), O_loc.shape, core.device
-        # float32 like _BceLossStream; float64 stand-ins of the steps (tests on the CPU) keep their precision
+        # float32 like _BceLoss1vN; float64 stand-ins of the steps (tests on the CPU) keep their precision
         ctx.ldt = ldt = torch.float64 if core.dtype == torch.float64 else torch.float32
-        ctx.eps, ctx.max_pos, ctx.B, ctx.mode = float(eps), int(max_pos), B, sigmoid_mode
+        ctx.eps, ctx.max_pos, ctx.B, ctx.mode, ctx.who = float(eps), int(max_pos), B, sigmoid_mode, who
         ctx.col0, ctx.n_ent, ctx.all_reduce, ctx.steps, ctx.has_dv = col0, n_ent, all_reduce, steps, want_dv
         if B == 0:
             ctx.save_for_backward(core, R, S, O_loc)
@@ -793,7 +711,7 @@ class _BceLossBlock(torch.autograd.Function):
     def backward(ctx, grad_loss):
         needs = ctx.needs_input_grad
         if ctx.B == 0:
-            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 13
+            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 14
         core, R, S, O_loc, h, r, v, qp, pair_slot, pair_ptr, pair_obj, dv = ctx.saved_tensors
         steps, B, dev = ctx.steps, ctx.B, core.device
         g = (grad_loss.to(device=dev, dtype=ctx.ldt).reshape(1) * (1.0 / (B * ctx.n_ent))).contiguous()
@@ -803,25 +721,26 @@ class _BceLossBlock(torch.autograd.Function):
                                ctx.mode, g) if O_loc.shape[0] > 0 else torch.zeros_like(O_loc))
         if any(needs[:3]):
             if not ctx.has_dv:
-                raise RuntimeError("bce_loss_block_1vN: dv was not computed in the forward")
+                raise RuntimeError(f"{ctx.who}: dv was not computed in the forward")
             if ctx.all_reduce is not None:       # dv, (B, c), never gS, (n_ent, b); the saved share stays as it is
                 dv = dv.clone()
                 ctx.all_reduce(dv)
             gcore, gR, gS = steps.stage1_backward(core, R, S, h, r, dv * g, needs)
-        return (gcore, gR, gS, gO) + (None,) * 13
+        return (gcore, gR, gS, gO) + (None,) * 14
 
 
 def _block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing,
-                sigmoid_mode, max_pos, all_reduce):
+                sigmoid_mode, max_pos, all_reduce, who="bce_loss_block_1vN"):
     dev = core.device
     slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
     if max_pos is None:
         mx = getattr(flt, "max_list", None)
         max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+    # dv (the second tile product of sweep 1) only when a gradient of core, R or S can be asked for
     want_dv = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S))
     return _BceLossBlock.apply(core, R, S, O_loc, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                                float(label_smoothing), sigmoid_mode, int(max_pos), want_dv, int(col0), int(n_ent),
-                               all_reduce, steps)
+                               all_reduce, steps, who)
 
 
 def bce_loss_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0,
@@ -1019,7 +938,9 @@ def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, wan
              tables=None):
     """Filtered rank of each ``(h, r, t)`` query against every entity -> int32 ``(B,)``, or ``(ranks, bce_rows float64)``
     with ``want_bce`` -- what ``evaluation.filtered_ranks`` gives on ``score_1vN``'s probabilities, without forming the
-    (B, N) score matrix (``rtk_score_rank_*``: one kernel scores and counts, no score is stored).  ``flt`` (a
+    (B, N) score matrix (``rtk_score_rank_*``: the kernels of ``rank_targets_block`` and ``rank_counts_block_1vN`` on the
+    whole range as one block -- target scores, an entity-stationary pass that scores and counts, the filter correction, a
+    finish pass; no score is stored).  ``flt`` (a
     ``DeviceFilter``): the other known-true objects of each query's pair count as probability 0.  Ranks are those of
     ``filtered_ranks`` over the fp32 ws score kernel's output (bf16 operands: the bf16 kernel's); the default fp32
     kernel differs from it only on ``cg_fifth_group_columns``.  Inference only.  An ``object_idx`` outside [0, N)

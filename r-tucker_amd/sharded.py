@@ -359,7 +359,7 @@ class ShardedEntityScorer:
                 return v, (self.pack_fn or ops.pack_query_vectors)(v, O_loc.dtype)
 
             steps = SimpleNamespace(
-                operands=lambda c_, R_, S_, O_, h, r, col0, n: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
+                operands=lambda c_, R_, S_, O_, h, r, col0, n, who: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
                 queries=queries if self.query_vectors_fn is not None else steps.queries,
                 rows=rows_fn or steps.rows, grad_o=grad_o_fn or steps.grad_o,
                 stage1_backward=stage1_bwd_fn or steps.stage1_backward)

@@ -1,6 +1,6 @@
 """GPU tests of filtered ranking on entity blocks without the score block (ops.rank_targets_block,
 ops.rank_counts_block_1vN, ShardedEntityScorer.rank_1vN; rtk_score_rank_targets_* / rtk_score_rank_counts_*,
-csrc/rtk_score_rank_part.hip).
+csrc/rtk_score_rank.hip).
 
 Ranks are integers and a probability's bits depend only on its query row, its entity row and c, so every check on
 counts is exact: for each way of cutting the entity range into blocks, 1 + the sum of the blocks' counts must EQUAL

@@ -1,6 +1,8 @@
 """The matrix-free training loss without a GPU: the workspace-size function, the argument checks of
 ``rtk_bce_stream_rows_f32`` / ``rtk_bce_stream_grad_o_f32`` (code and message before anything is enqueued), the
 bindings and the Python entry point's refusals."""
+from types import SimpleNamespace
+
 import pytest
 import torch
 
@@ -99,9 +101,15 @@ def test_symbols_bound(lib):
 
 def test_python_refusals_without_a_gpu():
     z = torch.zeros
+    flt = SimpleNamespace(slot_of_item=torch.tensor([0]), pair_ptr=torch.tensor([0, 1]), pair_obj=torch.tensor([0]),
+                          max_list=1)
     with pytest.raises(RuntimeError, match="no CPU path"):
-        rt.ops._BceLossStream.apply(z(2, 8, 8), z(3, 2), z(5, 8), z(5, 8), torch.tensor([0]), torch.tensor([0]),
-                                    torch.tensor([0]), torch.tensor([0, 1]), torch.tensor([0]), 0.1, None, 4, False)
+        rt.bce_loss_1vN(z(2, 8, 8), z(3, 2), z(5, 8), z(5, 8), torch.tensor([0]), torch.tensor([0]), flt,
+                        torch.tensor([0]), label_smoothing=0.1, matrix_free=True)
+    with pytest.raises(RuntimeError, match="no CPU path"):       # the autograd function itself: the whole matrix as one block
+        rt.ops._BceLossBlock.apply(z(2, 8, 8), z(3, 2), z(5, 8), z(5, 8), torch.tensor([0]), torch.tensor([0]),
+                                   torch.tensor([0]), torch.tensor([0, 1]), torch.tensor([0]), 0.1, None, 4, False, 0, 5,
+                                   None, rt.ops._HipBlockLoss)
     assert "matrix_free" in rt.bce_loss_1vN.__code__.co_varnames
     import inspect
     from r_tucker_amd import driver

@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Per-batch times of filtered ranking on ONE rank's block of entity rows, three ways, in one process, alternated:
+"""Per-batch times of filtered ranking on ONE rank's block of entity rows, two ways, in one process, alternated:
 
   (a) stored   the block path ShardedEntityScorer.filtered_ranks runs for a rank: score_1vN_into a (B, n_local) fp32
                block, target_scores_block, rank_counts_block;
-  (b) sweep    ops.rank_1vN on the same rows of O taken as a problem of their own (the query-stationary sweep_kernel:
-               its ranks are not the global ones, its work is the same);
   (c) blocks   the two matrix-free steps: stage 1 packed, ops.rank_targets_block, ops.rank_counts_block_1vN
                (count_kernel, entity-stationary).
+
+(The former variant (b), ops.rank_1vN on the same rows as a problem of their own, ran a query-stationary kernel that no
+longer exists: rank_1vN is now (c) at col0 = 0 in one library call; tools/rank_timing.py times it.)
 
 Shapes: WN18RR (fp32, c 200, B 512, N 40 943 as one block, test queries with their filter lists; with and without
 BCE), FB15k-237-like bf16 (c 200, B 2048, N 14 541) and one eighth of the 1 M-entity bf16 problem (c 512, B 8192,
@@ -47,24 +48,19 @@ def shape(name, core, R, S, O_loc, col0, n_ent, h, r, t, flt, items, tables, wan
     B, n_loc = h.numel(), O_loc.shape[0]
     block = torch.empty((B, n_loc), dtype=torch.float32, device="cuda")
     slots = flt.slots_of(h, r) if flt is not None else None
-    t_loc = (t - col0).clamp(0, n_loc - 1)                 # (b): a problem of its own needs ids inside it
 
     def stored():
         rt.score_1vN_into(core, R, S, O_loc, h, r, out=block, tables=tables)
         pt = target_scores_block(block, t, col0)
         return rank_counts_block(block, t, col0, pt, flt, items, want_bce)
 
-    def sweep():
-        return rt.rank_1vN(core, R, S, O_loc, h, r, t_loc, flt=flt if col0 == 0 else None, want_bce=want_bce, tables=tables)
-
     def blocks():
         _, qp = rt.query_vectors(core, R, S, h, r, tables=tables, packed=True)
         pt = rt.rank_targets_block(qp, B, O_loc, col0, n_ent, t)
         return rt.rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, t, flt=flt, slots=slots, want_bce=want_bce)
 
-    us = alternate({"stored": stored, "sweep": sweep, "blocks": blocks}, rounds, reps)
-    print(f"{name:44s} (a) stored {us['stored']:10.1f}  (b) sweep {us['sweep']:10.1f}  (c) blocks {us['blocks']:10.1f} us "
-          f"(wall clock per batch)")
+    us = alternate({"stored": stored, "blocks": blocks}, rounds, reps)
+    print(f"{name:44s} (a) stored {us['stored']:10.1f}  (c) blocks {us['blocks']:10.1f} us (wall clock per batch)")
 
 
 with rt.index_check("off"), torch.no_grad():

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Kernel times of filtered ranking without the score matrix (ops.rank_1vN: pair_kernel, sweep_kernel, pair_kernel)
+"""Kernel times of filtered ranking without the score matrix (ops.rank_1vN: target_kernel, count_kernel,
+filter_kernel, finish_kernel)
 next to the stored path it replaces (score_1vN + filtered_ranks); run under ``rocprofv3 --kernel-trace --stats`` for the
 per-kernel durations.
 
