@@ -16,9 +16,9 @@
 
 namespace {
 
-// ln x on v_log_f32 (log2, 1 ulp) -- the row sums are compute-bound on ocml's logf otherwise (62 us vs the
-// 15 us the 84 MB read takes at C2); torch clamps BCE's logs at -100
-__device__ __forceinline__ float clog(float x) { return fmaxf(__builtin_amdgcn_logf(x) * 0.6931471805599453f, -100.0f); }
+// ln x is rtk_clog (rtk_common.h): v_log_f32 (log2, 1 ulp) -- the row sums are compute-bound on ocml's logf otherwise
+// (62 us vs the 15 us the 84 MB read takes at C2); torch clamps BCE's logs at -100.  P is whatever the caller stored:
+// a subnormal probability (the exact logistic returns them) must not read as 0, ln 1e-40 is -92.1 and not -100.
 
 // one workgroup per row
 __global__ __launch_bounds__(256) void bce_rows_kernel(const float *__restrict__ P, int N, int64_t ld, float t0, float dt,
@@ -38,11 +38,11 @@ __global__ __launch_bounds__(256) void bce_rows_kernel(const float *__restrict__
 #pragma unroll
         for (int u = 0; u < U; ++u) p[u] = row[j + 256 * u];
 #pragma unroll
-        for (int u = 0; u < U; ++u) acc += t0 * clog(p[u]) + (1.0f - t0) * clog(1.0f - p[u]);
+        for (int u = 0; u < U; ++u) acc += t0 * rtk_clog(p[u]) + (1.0f - t0) * rtk_clog(1.0f - p[u]);
     }
     for (; j < N; j += 256) {
         const float p = row[j];
-        acc += t0 * clog(p) + (1.0f - t0) * clog(1.0f - p);
+        acc += t0 * rtk_clog(p) + (1.0f - t0) * rtk_clog(1.0f - p);
     }
     // the pair's known objects: y = t0 + dt, dt = 1 - eps
     const int64_t s = pair_slot[d];
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(256) void bce_rows_kernel(const float *__restrict__
         const int64_t j = pair_obj[i];
         if (j < 0 || j >= N) continue;
         const float p = row[j];
-        acc += dt * (clog(p) - clog(1.0f - p));
+        acc += dt * (rtk_clog(p) - rtk_clog(1.0f - p));
     }
     double a = (double)acc;
 #pragma unroll
@@ -62,7 +62,9 @@ __global__ __launch_bounds__(256) void bce_rows_kernel(const float *__restrict__
 
 // Pass 1, the positives (their target is t0 + dt): p <- p - dt unless p is saturated (p == 1.0f stays 1.0f and
 // is then zeroed by pass 2 like a saturated negative; an unsaturated positive lands in (-dt, 1 - dt), never
-// on 1.0f).  One workgroup per row.
+// on 1.0f).  A positive whose score EQUALS dt (0.9f is an ordinary fp32 value) would land on 0.0f and read as
+// saturated in pass 2: it is stored as the smallest denormal instead, like the fused path's marker
+// (rtk_score_split_kernel.h), and pass 2 returns (1.4e-45 - t0) s = -t0 s, bit for bit.  One workgroup per row.
 __global__ __launch_bounds__(64) void bce_grad_pos_kernel(float *__restrict__ P, int N, int64_t ld, float dt,
                                                           const int64_t *__restrict__ pair_slot,
                                                           const int64_t *__restrict__ pair_ptr,
@@ -74,7 +76,7 @@ __global__ __launch_bounds__(64) void bce_grad_pos_kernel(float *__restrict__ P,
         const int64_t j = pair_obj[i];
         if (j >= 0 && j < N) {
             const float p = row[j];
-            if (p != 1.0f && p != 0.0f) row[j] = p - dt;
+            if (p != 1.0f && p != 0.0f) row[j] = (p == dt) ? __builtin_bit_cast(float, 1u) : p - dt;
         }
     }
 }
@@ -111,6 +113,9 @@ __global__ __launch_bounds__(256) void bce_grad_all_kernel(float *__restrict__ P
 // and entity row -- one wave per row, the 64 lanes share each dot product -- and p from it by the kernel's own formula.  rows_pos holds PATCH_Y = 4 partial sums per row.
 // A stored zero is a score the kernel saw saturated (+0: 1.0f, -0: 0.0f): it stays zero (zero logit gradient, like the
 // reference's autograd) and its correction uses torch's clamp, ln 0 = -100.
+// ln p of a p recomputed by the fast logistic: the plain form of split_clog (rtk_score_split_kernel.h), the same bits
+// as the fused kernel's.  v_rcp_f32 returns no subnormal (see there), so there is nothing for rtk_clog to rescale.
+__device__ __forceinline__ float fast_clog(float x) { return fmaxf(__builtin_amdgcn_logf(x) * 0.6931471805599453f, -100.0f); }
 constexpr int PATCH_Y = 4;      // workgroups per row; 4 waves each: 16 positives of a row in flight (hub pairs have hundreds)
 __global__ __launch_bounds__(256) void bce_patch_pos_kernel(float *__restrict__ X, int N, int64_t ld, float t0, float dt,
                                                             const int64_t *__restrict__ pair_slot,
@@ -138,7 +143,7 @@ __global__ __launch_bounds__(256) void bce_patch_pos_kernel(float *__restrict__ 
                 acc += (__builtin_bit_cast(unsigned, x) >> 31) ? -dt * 100.0f : dt * 100.0f;
             } else {
                 const float p = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
-                acc += dt * (clog(p) - clog(1.0f - p));
+                acc += dt * (fast_clog(p) - fast_clog(1.0f - p));
                 row[j] = x - dt;
             }
         }

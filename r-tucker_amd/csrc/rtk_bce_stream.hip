@@ -220,7 +220,7 @@ __global__ __launch_bounds__(64 * BS_WAVES, 1) void rows_kernel(const unsigned c
                     const float p = SG == 2 ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[e] * s))
                                             : rtk_sigmoid(acc[e] * s);
                     x[e] = x_of(p, t0, valid);
-                    ls += valid ? t0 * clog(p) + (1.0f - t0) * clog(1.0f - p) : 0.f;
+                    ls += valid ? t0 * rtk_clog(p) + (1.0f - t0) * rtk_clog(1.0f - p) : 0.f;
                 }
             }
             lsum += (double)ls;
@@ -360,7 +360,7 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
                 const f32x16 acc = f.chain(A0, A1);
                 if (h == 0 && ok) {                                // element 0 of lane r: row 0, column r
                     const float p = f.template prob<SG>(acc[0], srow);
-                    lacc += dt * (clog(p) - clog(1.0f - p));
+                    lacc += dt * (rtk_clog(p) - rtk_clog(1.0f - p));
                     dz = (p == 1.0f || p == 0.0f) ? 0.f : -dt;
                 }
             }

@@ -134,4 +134,14 @@ template <typename T> __host__ __device__ constexpr int rtk_vec4_align() { retur
 // IEEE division, the same formula torch's CPU kernel evaluates; saturates to
 // exactly 1.0f for x >~ 16.64 like the reference.
 __device__ __forceinline__ float rtk_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+// ln x on v_log_f32 (log2, 1 ulp), clamped at -100 like torch's BCE.  v_log_f32 reads a subnormal x as 0, and the exact
+// logistic (an IEEE division) does return subnormal probabilities (ln p between -87.3 and -103.3), as may any score
+// matrix a caller hands in: those are scaled by 2^32 first.  A normal x gives the bits of the plain form.  The one
+// copy for every kernel that sums BCE terms of STORED or exactly computed probabilities (rtk_rank.hip,
+// rtk_score_rank_kernel.h, rtk_bce.hip), so that their bits stay equal.
+__device__ __forceinline__ float rtk_clog(float x) {
+    const bool sub = x < 1.17549435e-38f;
+    const float l2 = __builtin_amdgcn_logf(sub ? x * 4294967296.0f : x) - (sub ? 32.0f : 0.0f);
+    return fmaxf(l2 * 0.6931471805599453f, -100.0f);
+}
 #endif

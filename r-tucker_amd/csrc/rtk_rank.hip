@@ -19,14 +19,7 @@
 
 namespace {
 
-// ln x on v_log_f32 (log2, 1 ulp), clamped at -100 like torch's BCE.  v_log_f32 reads a subnormal x as 0, and the exact logistic (an
-// IEEE division) does return subnormal probabilities (ln p between -87.3 and -103.3): those are scaled by 2^32 first.
-// A normal x gives the bits of the plain form.
-__device__ __forceinline__ float clog(float x) {
-    const bool sub = x < 1.17549435e-38f;
-    const float l2 = __builtin_amdgcn_logf(sub ? x * 4294967296.0f : x) - (sub ? 32.0f : 0.0f);
-    return fmaxf(l2 * 0.6931471805599453f, -100.0f);
-}
+// (BCE logs: rtk_clog, rtk_common.h -- v_log_f32, clamped at -100 like torch's BCE, subnormal-safe)
 
 // PARTIAL: target scores come from pt_in, the "+1" is left to the caller, ids are global
 template <bool PARTIAL>
@@ -56,14 +49,14 @@ __global__ __launch_bounds__(256) void filtered_rank_kernel(
         for (int u = 0; u < U; ++u) {
             gt += p[u] > pt;
             eq += (p[u] == pt) & (j + 256 * u < tgt);
-            if (want_bce) bce += clog(1.0f - p[u]);
+            if (want_bce) bce += rtk_clog(1.0f - p[u]);
         }
     }
     for (; j < N; j += 256) {
         const float p = row[j];
         gt += p > pt;
         eq += (p == pt) & (j < tgt);
-        if (want_bce) bce += clog(1.0f - p);
+        if (want_bce) bce += rtk_clog(1.0f - p);
     }
     // the query's other true objects count as score 0 (and, for BCE, as positives)
     const int64_t s = pair_slot ? pair_slot[d] : -1;
@@ -72,14 +65,14 @@ __global__ __launch_bounds__(256) void filtered_rank_kernel(
             const int64_t j = pair_obj[i] - col0;
             if (j < 0 || j >= N) continue;
             const float p = row[j];
-            if (want_bce) bce += clog(p) - clog(1.0f - p);
+            if (want_bce) bce += rtk_clog(p) - rtk_clog(1.0f - p);
             if (j == tgt) continue;
             gt -= p > pt;
             eq -= (p == pt) & (j < tgt);
             eq += (0.0f == pt) & (j < tgt);     // now a 0: ties only with a zero target score
         }
     } else if (want_bce && t == 0 && own) {     // no filter list: the queried object is the only positive
-        bce += clog(pt) - clog(1.0f - pt);
+        bce += rtk_clog(pt) - rtk_clog(1.0f - pt);
     }
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(64 * RP_WAVES, 2) void count_kernel(const unsigned 
                     const float p = f.template prob<SG>(acc[e], sr4[q]);
                     const int k = (p > pt4[q]) + ((p == pt4[q]) & (jg < (int)tg4[q]));
                     cnt[e] = valid ? k : 0;
-                    bce[e] = (BCE && valid) ? clog(1.0f - p) : 0.f;
+                    bce[e] = (BCE && valid) ? rtk_clog(1.0f - p) : 0.f;
                 }
             }
             const int csum = reduce16(cnt, r);
@@ -275,7 +275,7 @@ __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned ch
                 const f32x16 acc = f.chain(A0, A1);
                 if (h == 0 && ok) {                                    // element 0 of lane r: row 0, column r
                     const float p = f.template prob<SG>(acc[0], srow);
-                    if (want_bce) bce += clog(p) - clog(1.0f - p);
+                    if (want_bce) bce += rtk_clog(p) - rtk_clog(1.0f - p);
                     if (jr != tgt) {
                         cnt -= p > pt;
                         cnt -= (p == pt) & (jr < tgt);
@@ -339,7 +339,7 @@ __global__ __launch_bounds__(256) void finish_kernel(int B, int n_slots, int col
     } else if (want_bce) {                                   // no filter list: the queried object is the only positive
         const int jl = clamp_target(obj_idx[d], n_ent) - col0;
         const float pt = pt_in[d];
-        if (jl >= 0 && jl < n_local) bce += (double)(clog(pt) - clog(1.0f - pt));
+        if (jl >= 0 && jl < n_local) bce += (double)(rtk_clog(pt) - rtk_clog(1.0f - pt));
     }
     counts_out[d] = base + cnt;
     if (want_bce) bce_rows_out[d] = -bce;

@@ -9,14 +9,7 @@
 
 namespace {
 
-// ln x on v_log_f32, clamped at -100 like torch's BCE.  v_log_f32 reads a subnormal x as 0, and the exact logistic (an
-// IEEE division) does return subnormal probabilities (ln p between -87.3 and -103.3): those are scaled by 2^32 first.
-// A normal x gives the bits of the plain form.
-__device__ __forceinline__ float clog(float x) {
-    const bool sub = x < 1.17549435e-38f;
-    const float l2 = __builtin_amdgcn_logf(sub ? x * 4294967296.0f : x) - (sub ? 32.0f : 0.0f);
-    return fmaxf(l2 * 0.6931471805599453f, -100.0f);
-}
+// (the clamped logarithm of the BCE terms is rtk_clog, rtk_common.h)
 
 // Operand form of one element type: B fragments of one entity row per lane pair (r, h), A fragments of the packed
 // planes, and the logistic of the accumulated value.

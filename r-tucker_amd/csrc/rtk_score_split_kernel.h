@@ -19,6 +19,10 @@ __device__ unsigned long long g_istamps[4096 * 8];   // ABL bit 7: s_memtime sta
 // BCE term -(t0 ln p + (1 - t0) ln(1 - p)) (logs on v_log_f32, clamped at -100 like torch) to a per-lane sum that
 // leaves the kernel as ONE double per workgroup in partials[blockIdx.x].  The few positives are patched afterwards
 // (rtk_bce.hip: bce_patch_pos_kernel).  The B x N matrix is written once and never re-read in the forward.
+// split_clog is the plain form, without rtk_clog's rescaling of subnormals (rtk_common.h), on purpose: its argument is
+// a probability from the fast logistic, and v_rcp_f32 returns no subnormal -- over z = -89.5 .. -87 in steps of 2^-10
+// the kernel's p goes from 1.1762094e-38 (z = -87.33594) straight to 0 -- while 1.0f - p is 0 or
+// at least 2^-24.  The epilogue lives in the MFMA shadow; it is not given VALU work that cannot change a bit.
 __device__ __forceinline__ float split_clog(float x) { return fmaxf(__builtin_amdgcn_logf(x) * 0.6931471805599453f, -100.0f); }
 
 template <int KS, int SIGMOID, int MINW, unsigned ABL = 0, bool LOSS = false>
