@@ -629,6 +629,53 @@ int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, int c, const
                                size_t ws_bytes, void *stream);
 
 /*
+ * Filtered top-k link prediction WITHOUT the (batch x n_ent) score matrix or a (batch x n_local) score block
+ * (rtk_score_topk.hip): values_out / ids_out are exactly what rtk_select_topk_f32 writes for the block's probabilities
+ * -- P (batch x n_local) of rtk_score_packed_f32 with RTK_SCORE_KERNEL_WS (_f32) or of rtk_score_packed_bf16's fp32
+ * scores (_bf16) on rows [col0, col0 + n_local) of O, selected with col0, the same CSR, keep_idx and k: values bit for
+ * bit, ids, the tie order (higher score, then lower id; -0 == +0; NaN above +inf), the (-inf, -1) padding.  The
+ * element arithmetic is that of rtk_score_rank_* (the same fragments), so a probability has the same bits in every
+ * block: the lists of any partition of [0, n_ent) into blocks, merged by rtk_select_topk_f32 in merge mode in
+ * ascending block order, equal the whole range's list (col0 = 0, n_local = n_ent).
+ * On the caller's stream, enqueue only (graph-capturable):
+ *   1. the maximum probability of every (query, tile of 128 entity rows), entity-stationary (every row of O_local is
+ *      converted into MFMA operands once per call, once per query range when n_local < 65 536);
+ *   2. with pair_slot: the tiles that hold a filtered object of a query are scored again for that query and their
+ *      maxima corrected to exclude the query's filtered objects;
+ *   3. rtk_select_topk_f32 on the maxima: the k_t = min(k, ceil(n_local / 128)) best tiles per query;
+ *   4. those tiles scored again, their 128 k_t probabilities and ids per query written in ascending id order;
+ *   5. rtk_select_topk_f32 in merge mode on these candidates.
+ * k tiles suffice: a tile left out is preceded by k tiles whose maxima are k distinct eligible objects, each ahead of
+ * every object of that tile (a larger value, or an equal one with a lower id).
+ *   q_packed   packed query planes of the batch (stage 1, as for rtk_score_packed_*)
+ *   pair_slot, pair_ptr, pair_obj, keep_idx   as rtk_select_topk_f32 (GLOBAL ids; entries outside the block are
+ *              ignored; an object listed twice is harmless); pair_slot and keep_idx may be NULL
+ *   k          1 <= k <= 128, else RTK_ERR_BAD_ARG
+ *   flags      RTK_SCORE_SIGMOID, optionally RTK_SCORE_SIGMOID_FAST: probabilities only (a masked row is -inf, which
+ *              no probability is); without RTK_SCORE_SIGMOID: RTK_ERR_UNSUPPORTED
+ *   workspace  rtk_score_topk_workspace_bytes (valid without a device; 0 for a k or c outside the covered range),
+ *              256-byte aligned, with T = ceil(n_local / 128), k_t = min(k, T), align256 rounding up to 256:
+ *                  256 + align256(4 batch T) + align256(4 batch k_t) + align256(8 batch k_t)
+ *                      + align256(512 batch k_t) + align256(1024 batch k_t)
+ *              -- only the first term grows with n_local, at 1/128 of the score block (256 MB at batch 8192,
+ *              n_local 1 000 000); callers bound the rest by splitting the batch, which is exact.  Its first 256 bytes
+ *              are the error word's header and are left alone.
+ * Covered shapes: _f32 c <= 208, c % 4 == 0, 16-byte-aligned O; _bf16 c <= 512; batch < 2^24.  Others give
+ * RTK_ERR_UNSUPPORTED.  Refused with RTK_ERR_BAD_ARG before anything is enqueued: null pointers, batch < 0, n_ent < 1,
+ * c < 1, a block outside [0, n_ent), pair_slot without the CSR arrays, unknown flags, a workspace too small or not
+ * 256-byte aligned.  batch == 0 returns at once.  Deterministic: one writer per value, no float atomics.
+ */
+size_t rtk_score_topk_workspace_bytes(int dtype, int64_t batch, int64_t n_local, int c, int k);
+int rtk_score_topk_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local, int64_t col0,
+                       int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                       const int64_t *keep_idx, int k, unsigned flags, float *values_out, int64_t *ids_out,
+                       void *workspace, size_t ws_bytes, void *stream);
+int rtk_score_topk_bf16(const void *q_packed, int64_t batch, int c, const void *O_local, int64_t n_local, int64_t col0,
+                        int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                        const int64_t *keep_idx, int k, unsigned flags, float *values_out, int64_t *ids_out,
+                        void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * The 1-vs-all BCE training loss and its gradients WITHOUT the (batch x n_ent) score matrix (rtk_bce_stream.hip): the
  * matrix-free form of rtk_score_packed_bce_f32 + rtk_bce_patch_pos_f32 and of the two batch x n_ent sized GEMMs of the
  * backward.  Same arithmetic: p = the ws score kernel's probability (Frag of rtk_score_rank_*, both logistic modes),

@@ -94,6 +94,9 @@ SIGNATURES = {
     "rtk_score_rank_targets_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _u, _p, _p, _sz, _p]),
     "rtk_score_rank_counts_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
     "rtk_score_rank_counts_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
+    "rtk_score_topk_workspace_bytes": (_sz, [_i, _i64, _i64, _i, _i]),
+    "rtk_score_topk_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i, _u, _p, _p, _p, _sz, _p]),
+    "rtk_score_topk_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i, _u, _p, _p, _p, _sz, _p]),
     "rtk_bce_stream_workspace_bytes": (_sz, [_i64, _i64, _i, _i64]),
     "rtk_bce_stream_rows_f32": (_i, [_p, _i64, _i, _p, _i64, _p, _p, _p, C.c_float, _u, _p, _p, _p, _sz, _p]),
     "rtk_bce_stream_grad_o_f32": (_i, [_p, _p, _i64, _i, _p, _i64, _p, _p, _p, _i64, C.c_float, _u, _p, _p, _p, _sz, _p]),

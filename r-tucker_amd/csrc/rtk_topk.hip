@@ -20,6 +20,7 @@
 // columns only and an object listed twice is harmless.  Merge mode (an ids matrix instead of col0) tests a candidate
 // id against the CSR segment directly; its rows are short.
 #include "rtk_common.h"
+#include "rtk_topk_key.h"
 
 namespace {
 
@@ -32,26 +33,6 @@ constexpr int TK_BINS = 2048;                  // 11-bit digits: 8 KiB of int32 
 constexpr int TK_WIN = 1 << 16;                // exclusion-bitmap window, columns (8 KiB)
 constexpr int TK_CAP = 4096;                   // LDS candidate list, entries (16 KiB keys + 16 KiB columns)
 // LDS: 8 + 8 + 32 + 12 (sort buffer) + < 1 KiB = 60 KiB per workgroup: two workgroups per CU (160 KiB)
-
-__device__ __forceinline__ uint32_t sel_key(float x) {
-    uint32_t u = __float_as_uint(x);
-    if ((u & 0x7fffffffu) > 0x7f800000u) u = 0x7fc00000u;   // every NaN -> +NaN, above +inf
-    if (u == 0x80000000u) u = 0u;                             // -0 -> +0
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ uint32_t sel_key(rtk_bf16 x) {
-    uint32_t u = x;
-    if ((u & 0x7fffu) > 0x7f80u) u = 0x7fc0u;
-    if (u == 0x8000u) u = 0u;
-    return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
-}
-// key 0 lies below every real key (-inf maps to 0x007fffff / 0x007f): the padding key
-__device__ __forceinline__ float sel_value(uint32_t k, float) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
-}
-__device__ __forceinline__ float sel_value(uint32_t k, rtk_bf16) {
-    return __uint_as_float(((k & 0x8000u) ? (k & 0x7fffu) : (~k & 0xffffu)) << 16);
-}
 
 __device__ __forceinline__ int lanes_below(unsigned long long m) {
     return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));

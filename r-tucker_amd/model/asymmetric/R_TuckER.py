@@ -72,7 +72,8 @@ class R_TuckER(TablesCacheMixin, nn.Module):
     def predict(self, subject_idx, relation_idx, k=10, flt=None, **kw):
         """The ``k`` most likely objects of each ``(subject, relation, ?)`` query, best first: ``(values, ids)``
         (``ops.topk_1vN``; ``flt``: a ``DeviceFilter`` whose known-true objects are left out).  In eval mode the
-        relation tables are built once and reused, as by the scoring closure."""
+        relation tables are built once and reused, as by the scoring closure.  Keywords go to ``ops.topk_1vN``:
+        ``matrix_free=True`` selects without storing any scores."""
         tables = kw.pop("tables", None)
         if tables is None:
             tables = self._cached_tables(self.core, self.R.weight)

@@ -885,7 +885,7 @@ def _topk_score_buffer(device, stream_ptr, B, N, dtype):
 
 @torch.no_grad()
 def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=None, sigmoid=True, sigmoid_mode=None,
-             score_dtype=torch.float32, tables=None, entity_block=None):
+             score_dtype=torch.float32, tables=None, entity_block=None, matrix_free=False):
     """Filtered top-k link prediction: the ``k`` most likely objects of every ``(h, r, ?)`` query, best first, as
     ``(values (B, k) float32, ids (B, k) int64)`` -- the filtered, stable descending sort of ``score_1vN``'s rows cut
     at k, without sorting them (``evaluation.filtered_topk``).  ``flt`` (a ``DeviceFilter``): the known-true objects
@@ -898,9 +898,33 @@ def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=Non
     ``entity_block=n``: the entities are scored ``n`` at a time into a (B, n) buffer (``score_packed_into`` on the packed
     query vectors), each block's top k is selected and merged into the running top k -- memory B x n instead of B x N.
     Block scores may differ from full-width scores in the last bits (the fp32 kernel's fifth column group depends on
-    the column count, ``cg_fifth_group_columns``); the result is exact for the scores as computed."""
+    the column count, ``cg_fifth_group_columns``); the result is exact for the scores as computed.
+    ``matrix_free=True``: no scores are stored at all (``topk_block_1vN`` on the whole range; ``rtk_score_topk_*``) --
+    memory B x N / 128 floats plus B x 128 k candidates, the queries taken in chunks that keep the workspace under
+    ``TOPK_STREAM_WS_BYTES``.  The result is exactly ``filtered_topk`` on the probabilities of the fp32 ws score kernel
+    (bf16 operands: the bf16 kernel's), the contract of ``rank_1vN``, and the same for every partition into blocks.
+    Probabilities only (``sigmoid=True``), float32 scores, ``k <= 128``, fp32 ``c <= 208`` with ``c % 4 == 0``, bf16
+    ``c <= 512``; not together with ``entity_block``.  Anything else raises: there is no fallback."""
     from .evaluation import filtered_topk
     k = int(k)
+    if matrix_free:
+        if entity_block is not None:
+            raise ValueError("matrix_free=True stores no scores: entity_block does not apply (pass one of the two)")
+        if score_dtype != torch.float32:
+            raise ValueError(f"matrix_free=True selects on float32 probabilities, got score_dtype = {score_dtype}")
+        if not sigmoid:
+            raise ValueError("matrix_free=True is taken on probabilities: sigmoid=True (raw logits are not covered)")
+        _check_topk_stream_k(k)
+        op = _Operands(core, R, S, O, subject_idx, relation_idx)
+        B, dev = op.B, op.dev
+        slots = flt.slots_of(op.h, op.r) if flt is not None else None
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.c))
+            if B > 0:
+                _strict_check(_stage1(op, sp, tables, None, qp), sp)
+        return topk_block_1vN(qp, B, op.O, 0, op.O.shape[0], k, flt=flt, slots=slots, keep_idx=keep_idx,
+                              sigmoid_mode=sigmoid_mode)
     if not 1 <= k <= 1024:
         raise ValueError(f"k = {k}: the selection takes 1 <= k <= 1024")
     op = _Operands(core, R, S, O, subject_idx, relation_idx)
@@ -1000,10 +1024,12 @@ class _Block:
         if self.col0 < 0 or self.n_loc < 1 or self.col0 + self.n_loc > self.n_ent:
             raise RuntimeError(f"block [{self.col0}, {self.col0} + {self.n_loc}) is not a non-empty part of "
                                f"[0, n_ent = {self.n_ent})")
-        nt = torch.as_tensor(object_idx).numel()
-        if nt != self.B:
-            raise RuntimeError(f"object_idx has {nt} entries for {self.B} queries")
-        self.t = _idx("object_idx", object_idx, dev)
+        self.t = None                                     # (the top-k step has no queried objects)
+        if object_idx is not None:
+            nt = torch.as_tensor(object_idx).numel()
+            if nt != self.B:
+                raise RuntimeError(f"object_idx has {nt} entries for {self.B} queries")
+            self.t = _idx("object_idx", object_idx, dev)
 
     def workspace(self, sp):
         return _workspace(self.dev, sp, _size("rtk_score_rank_part_workspace_bytes", self.dcode, self.B, self.n_loc, self.c))
@@ -1067,6 +1093,81 @@ def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, s
             flags, counts.data_ptr(), bce.data_ptr() if want_bce else None, ws.data_ptr(), ws.numel(), sp),
             "rtk_score_rank_counts")
     return (counts, bce) if want_bce else counts
+
+
+# Workspace bound of one rtk_score_topk_* call: topk_block_1vN takes the queries in chunks (multiples of the 32-query
+# packed tile) whose tile maxima and candidates fit.  Chunking by query is exact.
+TOPK_STREAM_WS_BYTES = 256 << 20
+TOPK_STREAM_MAX_K = 128
+
+
+def _check_topk_stream_k(k):
+    if not 1 <= k <= TOPK_STREAM_MAX_K:
+        raise ValueError(f"k = {k}: the matrix-free top-k takes 1 <= k <= {TOPK_STREAM_MAX_K}")
+
+
+def _topk_stream_chunk(dcode, B, n_loc, c, k):
+    """Queries per ``rtk_score_topk_*`` call: all B when their workspace fits ``TOPK_STREAM_WS_BYTES``, else the largest
+    multiple of 32 that does (at least 32)."""
+    if B <= 32 or _size("rtk_score_topk_workspace_bytes", dcode, B, n_loc, c, k) <= TOPK_STREAM_WS_BYTES:
+        return B
+    n_tiles = -(-n_loc // 128)
+    per_query = 4 * n_tiles + (4 + 8 + 128 * 12) * min(k, n_tiles)
+    return max(32, (TOPK_STREAM_WS_BYTES - 6 * 256) // per_query // 32 * 32)
+
+
+@torch.no_grad()
+def topk_block_1vN(qp, B, O_loc, col0, n_ent, k, flt=None, slots=None, keep_idx=None, sigmoid_mode=None):
+    """Filtered top k of every query among the entity block ``O_loc`` = rows ``[col0, col0 + n_local)`` of the
+    (n_ent, c) entity matrix -> ``(values (B, k) float32, ids (B, k) int64)``, GLOBAL ids, best first, padded with
+    (-inf, -1); nothing of size B x n_local is written (``rtk_score_topk_*``: tile maxima in an entity-stationary
+    pass, their correction for the filter, the k best tiles, their candidates, the select).  The sibling of
+    ``rank_counts_block_1vN``: ``qp`` are packed query planes, ``flt`` (a ``DeviceFilter``) with ``slots``
+    (``flt.slots_of(h, r)``) removes each query's known-true objects except ``keep_idx[d]``.  Exactly
+    ``filtered_topk(P, k, flt, slots=slots, keep_idx=keep_idx, col0=col0)`` on the block's probabilities P of the fp32
+    ws score kernel (bf16 operands: the bf16 kernel's); the lists of the blocks of any partition of [0, n_ent),
+    concatenated in ascending block order and merged with ``filtered_topk(values, k, ids=ids)``, equal the whole
+    range's list.  Limits as ``topk_1vN(matrix_free=True)``."""
+    k = int(k)
+    _check_topk_stream_k(k)
+    b = _Block(qp, B, O_loc, col0, n_ent, None)
+    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
+    if flt is not None:
+        if slots is None:
+            raise ValueError("filtering needs the queries' filter slots: slots=flt.slots_of(subject_idx, relation_idx)")
+        slots = _idx("slots", slots, b.dev)
+        if slots.numel() != b.B:
+            raise RuntimeError(f"slots has {slots.numel()} entries for {b.B} queries")
+    elif slots is not None:
+        raise ValueError("slots need flt (the DeviceFilter that holds the CSR)")
+    if keep_idx is not None:
+        keep_idx = _idx("keep_idx", keep_idx, b.dev)
+        if keep_idx.numel() != b.B:
+            raise RuntimeError(f"keep_idx has {keep_idx.numel()} entries for {b.B} queries")
+    if _size("rtk_score_topk_workspace_bytes", b.dcode, max(b.B, 1), b.n_loc, b.c, k) == 0:
+        raise RuntimeError(f"topk_block_1vN: object rank c = {b.c} is not covered (float32: c <= 208 and c % 4 == 0; "
+                           "bfloat16: c <= 512); there is no fallback")
+    values = torch.empty((b.B, k), dtype=torch.float32, device=b.dev)
+    ids = torch.empty((b.B, k), dtype=torch.int64, device=b.dev)
+    if b.B == 0:
+        return values, ids
+    chunk = _topk_stream_chunk(b.dcode, b.B, b.n_loc, b.c, k)
+    tile_bytes = _size("rtk_packed_query_bytes", b.dcode, 32, b.c)
+    fn = _entry("rtk_score_topk", b.bf16)
+    with torch.cuda.device(b.dev):
+        sp = _stream_ptr(b.dev)
+        ws = _workspace(b.dev, sp, _size("rtk_score_topk_workspace_bytes", b.dcode, min(chunk, b.B), b.n_loc, b.c, k))
+        for q0 in range(0, b.B, chunk):
+            nq = min(chunk, b.B - q0)
+            _lib.check(fn(
+                b.qp.data_ptr() + (q0 // 32) * tile_bytes, nq, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent,
+                slots.data_ptr() + 8 * q0 if flt is not None else None,
+                flt.pair_ptr.data_ptr() if flt is not None else None,
+                flt.pair_obj.data_ptr() if flt is not None else None,
+                keep_idx.data_ptr() + 8 * q0 if keep_idx is not None else None,
+                k, flags, values.data_ptr() + 4 * k * q0, ids.data_ptr() + 8 * k * q0, ws.data_ptr(), ws.numel(), sp),
+                "rtk_score_topk")
+    return values, ids
 
 
 def _candidates(name, t, B, dev):

@@ -372,7 +372,7 @@ class ShardedEntityScorer:
 
     # ---- top-k without the gather ----------------------------------------------------------
     def topk(self, core, R, S, O_loc, subject_idx, relation_idx, k, flt=None, slots=None, keep_idx=None,
-             local_topk_fn=None, merge_fn=None, **kw):
+             local_topk_fn=None, merge_fn=None, matrix_free=False, **kw):
         """Filtered top-k objects (``(values, ids)``, (B, k), global entity ids, best first) with the entity matrix
         row-sharded and NO exchange of scores: each rank scores its block and selects its top k over its real
         columns (``col0 = rank * n_loc``; the last shard's padding rows are never candidates), the (B, k) lists are
@@ -380,7 +380,16 @@ class ShardedEntityScorer:
         gathered matrix.  ``slots`` default to ``flt.slots_of(subject_idx, relation_idx)``.
 
         ``local_topk_fn(P_block, k, col0, flt, slots, keep_idx)`` / ``merge_fn(values, ids, k)`` default to the HIP
-        select (``evaluation.filtered_topk``, plain and merge mode); tests inject CPU functions."""
+        select (``evaluation.filtered_topk``, plain and merge mode); tests inject CPU functions.
+
+        ``matrix_free=True``: the (B, n_loc) score block is not formed either.  Stage 1 goes into packed query planes
+        and the local step is ``ops.topk_block_1vN`` on this rank's real rows (``local_topk_fn`` then takes ITS
+        arguments: ``(qp, B, O_rows, col0, n_ent, k, flt=, slots=, keep_idx=, sigmoid_mode=)``); all-gather and merge
+        are the same.  Equals ``ops.topk_1vN(..., matrix_free=True)`` on the whole entity matrix exactly.  Keywords:
+        ``tables``, ``sigmoid_mode``."""
+        if matrix_free:
+            return self._topk_matrix_free(core, R, S, O_loc, subject_idx, relation_idx, k, flt, slots, keep_idx,
+                                          local_topk_fn, merge_fn, **kw)
         if local_topk_fn is None or merge_fn is None:
             from .evaluation import filtered_topk
             local_topk_fn = local_topk_fn or (lambda P, k_, col0, flt_, slots_, keep_: filtered_topk(
@@ -395,6 +404,31 @@ class ShardedEntityScorer:
         mine = g[self.rank][:, :n_loc]
         self._score_local(core, R, S, O_loc, subject_idx, relation_idx, mine, **kw)
         values, ids = local_topk_fn(mine[:, :n_valid], k, lo, flt, slots, keep_idx)
+        return self._merge_topk(values, ids, B, k, merge_fn)
+
+    def _topk_matrix_free(self, core, R, S, O_loc, subject_idx, relation_idx, k, flt, slots, keep_idx, local_topk_fn,
+                          merge_fn, tables=None, sigmoid_mode=None):
+        if local_topk_fn is None:
+            from .ops import topk_block_1vN as local_topk_fn
+        if merge_fn is None:
+            from .evaluation import filtered_topk
+            merge_fn = lambda v, i, k_: filtered_topk(v, k_, ids=i)                      # noqa: E731
+        B = int(subject_idx.numel())
+        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
+        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
+        if slots is None and flt is not None:
+            slots = flt.slots_of(subject_idx, relation_idx)
+        qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)
+        if n_valid > 0:
+            values, ids = local_topk_fn(qp, B, O_loc[:n_valid], lo, self.shards.n_ent, k, flt=flt, slots=slots,
+                                        keep_idx=keep_idx, sigmoid_mode=sigmoid_mode)
+        else:                                                     # a rank without rows: an empty list
+            values = torch.full((B, k), float("-inf"), dtype=torch.float32, device=core.device)
+            ids = torch.full((B, k), -1, dtype=torch.int64, device=core.device)
+        return self._merge_topk(values, ids, B, k, merge_fn)
+
+    def _merge_topk(self, values, ids, B, k, merge_fn):
+        """The ranks' (B, k) lists all-gathered and merged (one rank: its list is the result)."""
         if self.world == 1:
             return values, ids
         gv = torch.empty((self.world, B, k), dtype=values.dtype, device=values.device)
