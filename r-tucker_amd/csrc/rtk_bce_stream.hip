@@ -14,8 +14,8 @@
 //                 (the chain's operand with the per-row scaling of Frag, and the k-permuted transposed operand of the
 //                 dv product with one scale for all of O).  The BCE terms of the tile are summed per query.  The entity
 //                 range is cut into `splits` parts; slabs and loss partials are added by finish_kernel in split order.
-//   go_kernel     sweep 2, count_kernel's skeleton (rtk_score_rank.hip): a wave converts its 32 entity rows once,
-//                 sweeps the query tiles staged through LDS together with the packed tile of s v, and accumulates
+//   go_kernel     sweep 2, the entity-stationary sweep of rtk_score_rank_kernel.h: a wave converts its 32 entity rows
+//                 once, sweeps the query tiles staged through LDS together with the packed tile of s v, and accumulates
 //                 gO[j, :] += sum_d x[d, j] (s v[d, :]).  Here the entity is on the lane and the tile is the A operand
 //                 of X^T V.  A wave owns its 32 rows of gO: one read-add-store on top of the positives' share.
 //   pos_kernel    the positives: one workgroup per query re-scores the query's CSR entries with Frag (the sweeps' bits),
@@ -41,8 +41,8 @@ int rtk_cand_flat_scatter(const char *fn, const int32_t *ent, const int32_t *own
 
 namespace {
 
-constexpr int BS_WAVES = 4;
-constexpr int BS_MAX_KS = RTK_CG_MAX_KS;       // Frag<float, KS>'s range: c <= 208
+constexpr int BS_WAVES = SW_WAVES;
+constexpr int BS_MAX_KS = SW_MAX_KS_F32;       // Frag<float, KS>'s range: c <= 208
 constexpr int BS_POS_Y = 4;                    // loss partials per query of pos_kernel (one per wave)
 constexpr float BS_X_UP = 16384.0f;            // |x| <= 1 scaled to 2^14 before the hi/lo split
 
@@ -158,9 +158,9 @@ __global__ __launch_bounds__(64 * BS_WAVES, 1) void rows_kernel(const unsigned c
         mx = fmaxf(mx, __shfl_xor(mx, 1));
         mx = fmaxf(mx, __shfl_xor(mx, 2));
         mx = fmaxf(mx, __shfl_xor(mx, 4));
-        const int sh = rtk_pack_shift(mx);                          // Frag::convert's scaling of the row
-        const float up = ldexpf(1.0f, sh), us_o = ldexpf(1.0f, -sh);
-        if (part == 0) reinterpret_cast<float *>(lds + L::KC)[srw] = SG == 2 ? us_o * -1.4426950408889634f : us_o;
+        float up, kc;
+        Frag<float, KS>::template row_scale<SG>(mx, up, kc);
+        if (part == 0) reinterpret_cast<float *>(lds + L::KC)[srw] = kc;
         _Float16 *t2 = reinterpret_cast<_Float16 *>(lds + L::T2);
 #pragma unroll
         for (int i = 0; i < NF; ++i) {
@@ -216,9 +216,7 @@ __global__ __launch_bounds__(64 * BS_WAVES, 1) void rows_kernel(const unsigned c
                 for (int q = 0; q < 4; ++q) {
                     const int e = 4 * g + q;
                     const bool valid = tile * 32 + 8 * g + 4 * h + q < N;
-                    const float s = srow * kc4[q];                  // Frag::prob
-                    const float p = SG == 2 ? __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[e] * s))
-                                            : rtk_sigmoid(acc[e] * s);
+                    const float p = Frag<float, KS>::template logistic<SG>(acc[e], srow, kc4[q]);
                     x[e] = x_of(p, t0, valid);
                     ls += valid ? t0 * rtk_clog(p) + (1.0f - t0) * rtk_clog(1.0f - p) : 0.f;
                 }
@@ -242,7 +240,7 @@ __global__ __launch_bounds__(64 * BS_WAVES, 1) void rows_kernel(const unsigned c
         for (int ct = 0; ct < NCT; ++ct)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int dq = mt * 32 + 8 * (e >> 2) + 4 * h + (e & 3);
+                const int dq = mt * 32 + acc_row(e, h);
                 if (dq < B) slab[((int64_t)sp * B + dq) * CP + ct * 32 + r] = dacc[ct][e];
             }
     }
@@ -344,10 +342,8 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
     float lacc = 0.f;
     float dva[4] = {0.f, 0.f, 0.f, 0.f};
     if (i0 + 32 * wave < i1) {
-        const int mt = d >> 5, row = d & 31;
-        f16x8 A0[KS], A1[KS];
-        load_a<float, KS>(qp, mt, row, h, A0, A1);
-        const float srow = reinterpret_cast<const float *>(qp + mt * tile_bytes<float, KS>())[row];
+        QueryRow<float, KS> q;
+        q.load(qp, d, h);
         Frag<float, KS> f;
         for (int64_t base = i0 + 32 * wave; base < i1; base += 32 * BS_WAVES) {       // wave-uniform
             const int64_t i = base + r;
@@ -355,11 +351,8 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
             const bool ok = jr >= 0 && jr < N;
             float dz = 0.f;
             if (__ballot(ok) != 0) {
-                f.load(O, ok ? jr : 0, c, h, true);
-                f.template convert<SG>();
-                const f32x16 acc = f.chain(A0, A1);
+                const float p = q.template score<SG>(f, O, ok ? jr : 0, c, h, true);
                 if (h == 0 && ok) {                                // element 0 of lane r: row 0, column r
-                    const float p = f.template prob<SG>(acc[0], srow);
                     lacc += dt * (rtk_clog(p) - rtk_clog(1.0f - p));
                     dz = (p == 1.0f || p == 0.0f) ? 0.f : -dt;
                 }
@@ -426,8 +419,75 @@ __global__ __launch_bounds__(256) void pack_v_kernel(const float *__restrict__ v
 template <int KS>
 struct GoLds {
     static constexpr int TILE = (int)tile_bytes<float, KS>();      // the packed query tile (header + two planes)
-    static constexpr int BUF = TILE + timg_bytes(KS);              // ... and the tile's image of s v behind it
-    static constexpr int TOTAL = 2 * BUF;
+    static constexpr int EXTRA = timg_bytes(KS);                   // ... and the tile's image of s v behind it
+    static constexpr int TOTAL = 2 * (TILE + EXTRA);
+};
+
+// What go_kernel does with the sweep: the tile of x is the A operand of X^T V against the image of s v that travels
+// with the query tile; a wave's 32 rows of gO are accumulated over the query tiles and stored once per entity tile.
+template <int KS, int SG>
+struct GoSweep {
+    static constexpr int NCT = nct_of(KS);
+    static constexpr int EXTRA = GoLds<KS>::EXTRA;
+    static constexpr int NLV = EXTRA / 16 / (64 * BS_WAVES);        // 16-byte pieces of the image per thread: NCT
+    static_assert(EXTRA % (16 * 64 * BS_WAVES) == 0, "the image of s v is staged without a bound: whole pieces per thread");
+    const unsigned char *__restrict__ vp;
+    int B, N, c;
+    float t0, un;
+    float *__restrict__ gO;
+    u32x4 vstg[NLV];
+    f32x16 gacc[NCT];
+
+    __device__ __forceinline__ void load_extra(SweepLane ln, int mt) {
+        const u32x4 *sv = reinterpret_cast<const u32x4 *>(vp + (int64_t)mt * EXTRA);
+#pragma unroll
+        for (int i = 0; i < NLV; ++i) vstg[i] = sv[i * 64 * BS_WAVES + ln.t];
+    }
+    __device__ __forceinline__ void store_extra(SweepLane ln, int extra) const {
+        u32x4 *dst = reinterpret_cast<u32x4 *>(sweep_lds + extra);
+#pragma unroll
+        for (int i = 0; i < NLV; ++i) dst[i * 64 * BS_WAVES + ln.t] = vstg[i];
+    }
+    __device__ __forceinline__ void begin_tile() {
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) gacc[ct] = zero16();
+    }
+    // element e: query row acc_row(e, h) of the tile, entity r of the wave
+    __device__ __forceinline__ void score(SweepLane ln, const Frag<float, KS> &f, const f32x16 &acc,
+                                          const unsigned char *buf, int, int, bool, int mt) {
+        float x[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int rw = acc_row(4 * g, ln.h);
+            const f32x4 sr4 = *reinterpret_cast<const f32x4 *>(buf + rw * 4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const float p = f.template prob<SG>(acc[4 * g + q], sr4[q]);
+                x[4 * g + q] = x_of(p, t0, mt * 32 + rw + q < B);
+            }
+        }
+        f16x8 xh[2], xl[2];
+        split_x(x, xh, xl);
+        tile_product<NCT>(xh, xl, reinterpret_cast<const f16x8 *>(buf + GoLds<KS>::TILE), ln.lane, gacc);
+    }
+    __device__ __forceinline__ void publish(SweepLane, int, int, int, int, int, bool) const {}
+    // element e of gacc[ct]: entity row acc_row(e, h) of the wave, column 32 ct + r; on top of the positives' share
+    // that the ordered scatter wrote
+    __device__ __forceinline__ void end_tile(SweepLane ln, int tile) const {
+        const int j0 = tile * SW_TILE + ln.wave * 32;                // the wave's first row
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) {
+            const int col = ct * 32 + ln.r;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int j = j0 + acc_row(e, ln.h);
+                if (j < N && col < c) {
+                    float *dst = gO + (int64_t)j * c + col;
+                    *dst = gacc[ct][e] * un + *dst;
+                }
+            }
+        }
+    }
 };
 
 // Sweep 2.  Workgroup w: entity tiles (128 rows) w, w + grid, ...; every query tile.
@@ -436,91 +496,8 @@ __global__ __launch_bounds__(64 * BS_WAVES, 1) void go_kernel(const unsigned cha
                                                               const unsigned char *__restrict__ vp, int B,
                                                               const float *__restrict__ O, int N, int c, float t0,
                                                               const float *__restrict__ v_bound, float *__restrict__ gO) {
-    typedef GoLds<KS> L;
-    constexpr int NCT = nct_of(KS);
-    constexpr int NT = 64 * BS_WAVES;
-    constexpr int CH_Q = L::TILE / 16, CH = L::BUF / 16;
-    constexpr int NLD = (CH + NT - 1) / NT;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int n_mt = (B + 31) >> 5, n_tiles = (N + 32 * BS_WAVES - 1) / (32 * BS_WAVES);
-    const float un = ldexpf(1.0f, -14 - rtk_pack_shift(v_bound[0]));
-
-    u32x4 stg[NLD];
-    auto stage_load = [&](int mt) {
-        const u32x4 *sq = reinterpret_cast<const u32x4 *>(qp + (int64_t)mt * L::TILE);
-        const u32x4 *sv = reinterpret_cast<const u32x4 *>(vp + (int64_t)mt * timg_bytes(KS));
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int ch = i * NT + t;
-            if (ch < CH_Q) stg[i] = sq[ch];
-            else if (ch < CH) stg[i] = sv[ch - CH_Q];
-        }
-    };
-    auto stage_store = [&](int buf) {
-        u32x4 *dst = reinterpret_cast<u32x4 *>(lds + buf * L::BUF);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int ch = i * NT + t;
-            if (ch < CH) dst[ch] = stg[i];
-        }
-    };
-
-    stage_load(0);
-    int it = 0;
-    for (int tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
-        const int j0 = tile * 32 * BS_WAVES + wave * 32;             // the wave's first row
-        Frag<float, KS> f;
-        f.load(O, min(j0 + r, N - 1), c, h, true);
-        f.template convert<SG>();
-        f32x16 gacc[NCT];
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) gacc[ct] = zero16();
-        if (tile == (int)blockIdx.x) {
-            stage_store(0);
-            __syncthreads();
-        }
-        for (int i = 0; i < n_mt; ++i, ++it) {
-            const int cur = it & 1;
-            const bool more = i + 1 < n_mt || tile + (int)gridDim.x < n_tiles;
-            if (more) stage_load(i + 1 < n_mt ? i + 1 : 0);
-            const unsigned char *buf = lds + cur * L::BUF;
-            const f16x8 *la = reinterpret_cast<const f16x8 *>(buf + RTK_PACK_HDR);
-            const f32x16 acc = f.chain_with([&](int plane, int ks) { return la[(plane * KS + ks) * 64 + lane]; });
-            // element e: query row 8 (e / 4) + 4 h + e % 4 of the tile, entity r of the wave
-            float x[16];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int rw = 8 * g + 4 * h;
-                const f32x4 sr4 = *reinterpret_cast<const f32x4 *>(buf + rw * 4);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float p = f.template prob<SG>(acc[4 * g + q], sr4[q]);
-                    x[4 * g + q] = x_of(p, t0, i * 32 + rw + q < B);
-                }
-            }
-            f16x8 xh[2], xl[2];
-            split_x(x, xh, xl);
-            tile_product<NCT>(xh, xl, reinterpret_cast<const f16x8 *>(buf + L::TILE), lane, gacc);
-            if (more) stage_store(cur ^ 1);
-            __syncthreads();
-        }
-        // element e of gacc[ct]: entity row 8 (e / 4) + 4 h + e % 4 of the wave, column 32 ct + r; on top of the
-        // positives' share that the ordered scatter wrote
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const int col = ct * 32 + r;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int j = j0 + 8 * (e >> 2) + 4 * h + (e & 3);
-                if (j < N && col < c) {
-                    float *dst = gO + (int64_t)j * c + col;
-                    *dst = gacc[ct][e] * un + *dst;
-                }
-            }
-        }
-    }
+    GoSweep<KS, SG> pol{vp, B, N, c, t0, ldexpf(1.0f, -14 - rtk_pack_shift(v_bound[0])), gO};
+    sweep<float, KS, SG>(pol, qp, B, O, N, c, true, (int)gridDim.x, 1);
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------
@@ -561,35 +538,19 @@ StreamWs layout_of(int64_t batch, int c, int64_t max_pos) {
     return L;
 }
 
+// what rows and grad_o check alike (max_pos = 0 for rows)
 int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, const float *O, int64_t n_local, int64_t col0,
                  int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos, float eps,
                  unsigned flags, const void *out, const void *workspace, size_t ws_bytes) {
-    RTK_REQUIRE(q_packed && O && pair_slot && pair_ptr && pair_obj && out && workspace, RTK_ERR_BAD_ARG, "%s: null operand",
-                fn);
-    RTK_REQUIRE(batch >= 0, RTK_ERR_BAD_ARG, "%s: batch = %lld must be >= 0", fn, (long long)batch);
-    RTK_REQUIRE(n_ent >= 1, RTK_ERR_BAD_ARG, "%s: n_ent = %lld must be >= 1", fn, (long long)n_ent);
-    RTK_REQUIRE(col0 >= 0 && n_local >= 1 && n_local <= n_ent && col0 <= n_ent - n_local, RTK_ERR_BAD_ARG,
-                "%s: block [col0 = %lld, + n_local = %lld) is not a non-empty part of [0, n_ent = %lld)", fn, (long long)col0,
-                (long long)n_local, (long long)n_ent);
-    RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
-    RTK_REQUIRE(c >= 1, RTK_ERR_BAD_ARG, "%s: object rank c = %d must be >= 1", fn, c);
-    RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
-    RTK_REQUIRE(batch < (1ll << 31) - 32 && n_ent < (1ll << 31) - 256 && max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED,
-                "%s: dimension too large", fn);
-    RTK_REQUIRE(flags & RTK_SCORE_SIGMOID, RTK_ERR_UNSUPPORTED,
-                "%s: the loss is taken on probabilities: flags need RTK_SCORE_SIGMOID", fn);
-    RTK_REQUIRE((flags & ~(RTK_SCORE_SIGMOID | RTK_SCORE_SIGMOID_FAST)) == 0, RTK_ERR_BAD_ARG, "%s: unknown flags 0x%x",
-                fn, flags);
-    RTK_REQUIRE(c <= 16 * BS_MAX_KS, RTK_ERR_UNSUPPORTED,
-                "%s: c = %d above %d (the matrix-free loss keeps a whole row of the accumulator in one wave)", fn, c,
-                16 * BS_MAX_KS);
-    RTK_REQUIRE(c % 4 == 0 && (reinterpret_cast<uintptr_t>(O) & 15) == 0, RTK_ERR_UNSUPPORTED,
-                "%s: fp32 needs c %% 4 == 0 and a 16-byte-aligned O (c = %d)", fn, c);
-    const size_t need = layout_of(batch, c, max_pos).total;
-    RTK_REQUIRE(ws_bytes >= need, RTK_ERR_BAD_ARG, "%s: workspace of %zu bytes given, %zu needed", fn, ws_bytes, need);
-    RTK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, RTK_ERR_BAD_ARG, "%s: workspace must be 256-byte aligned",
-                fn);
-    return RTK_OK;
+    const auto own = [&]() -> int {
+        RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
+        RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
+        RTK_REQUIRE(max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
+        return RTK_OK;
+    };
+    return check_block(fn, q_packed && pair_slot && pair_ptr && pair_obj && out, batch, c, O, n_local, col0, n_ent, own,
+                       (1ll << 31) - 256, flags, "the loss is", workspace, ws_bytes,
+                       [&] { return layout_of(batch, c, max_pos).total; });
 }
 
 template <int KS, int SG>
@@ -651,16 +612,11 @@ int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const f
     }
     rc = rtk_cand_flat_scatter(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
     if (rc != RTK_OK) return rc;
-    constexpr int bytes = GoLds<KS>::TOTAL;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (bytes > 64 * 1024) {
-        rc = rtk_ensure_dynamic_lds(reinterpret_cast<const void *>(&go_kernel<KS, SG>), bytes, lds_ok, fn);
-        if (rc != RTK_OK) return rc;
-    }
-    const int64_t n_tiles = rtk_cdiv(N, 32 * BS_WAVES);
-    RTK_LAUNCH_SCORE((go_kernel<KS, SG>), dim3((unsigned)(n_tiles < RTK_N_CU ? n_tiles : RTK_N_CU)), dim3(64 * BS_WAVES), bytes,
-                     st, qp, ws + L.vp, B, O, N, c, t0, bounds + 1, gO);
-    return RTK_OK;
+    // one workgroup per CU: whole entity tiles per slot, no query ranges
+    const int n_slots = grid_of(B, N, RTK_N_CU).n_slots;
+    return launch_lds<&go_kernel<KS, SG>, GoLds<KS>::TOTAL>(dim3((unsigned)n_slots), dim3(64 * BS_WAVES), st, fn, qp,
+                                                            (const unsigned char *)(ws + L.vp), B, O, N, c, t0,
+                                                            (const float *)(bounds + 1), gO);
 }
 
 // The two sweeps on rows [col0, col0 + n_local) of the (n_ent x c) matrix; the whole matrix is the block (0, n_ent).
@@ -671,19 +627,11 @@ int stream_rows(const char *fn, const void *q_packed, int64_t batch, int c, cons
                           loss_rows_out, workspace, ws_bytes);
     if (rc != RTK_OK || batch == 0) return rc;
     const StreamWs L = layout_of(batch, c, 0);
-    const bool fast = (flags & RTK_SCORE_SIGMOID_FAST) != 0;
-    const unsigned char *qp = (const unsigned char *)q_packed;
-    unsigned char *ws = (unsigned char *)workspace;
-    hipStream_t st = (hipStream_t)stream;
-    rc = rtk_dispatch_ksteps<BS_MAX_KS>((c + 15) / 16, fn, [&](auto K) {
-        if (fast)
-            return launch_rows<K.value, 2>(qp, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
-                                           pair_obj, eps, loss_rows_out, dv_out, ws, L, st, fn);
-        return launch_rows<K.value, 1>(qp, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
-                                       pair_obj, eps, loss_rows_out, dv_out, ws, L, st, fn);
+    return dispatch<float>(fn, c, flags, [&](auto K, auto SG) {
+        return launch_rows<K.value, SG.value>((const unsigned char *)q_packed, (int)batch, c, O, (int)n_local, (int)col0,
+                                              (int)n_ent, pair_slot, pair_ptr, pair_obj, eps, loss_rows_out, dv_out,
+                                              (unsigned char *)workspace, L, (hipStream_t)stream, fn);
     });
-    if (rc != RTK_OK) return rc;
-    return rtk_check_launch(fn);
 }
 
 int stream_grad_o(const char *fn, const void *q_packed, const float *v, int64_t batch, int c, const float *O, int64_t n_local,
@@ -703,18 +651,11 @@ int stream_grad_o(const char *fn, const void *q_packed, const float *v, int64_t 
         return RTK_OK;
     }
     const StreamWs L = layout_of(batch, c, max_pos);
-    const bool fast = (flags & RTK_SCORE_SIGMOID_FAST) != 0;
-    const unsigned char *qp = (const unsigned char *)q_packed;
-    unsigned char *ws = (unsigned char *)workspace;
-    rc = rtk_dispatch_ksteps<BS_MAX_KS>((c + 15) / 16, fn, [&](auto K) {
-        if (fast)
-            return launch_grad_o<K.value, 2>(qp, v, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
-                                             pair_obj, max_pos, eps, scale, gO_out, ws, L, st, fn);
-        return launch_grad_o<K.value, 1>(qp, v, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent, pair_slot, pair_ptr,
-                                         pair_obj, max_pos, eps, scale, gO_out, ws, L, st, fn);
+    return dispatch<float>(fn, c, flags, [&](auto K, auto SG) {
+        return launch_grad_o<K.value, SG.value>((const unsigned char *)q_packed, v, (int)batch, c, O, (int)n_local, (int)col0,
+                                                (int)n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps, scale, gO_out,
+                                                (unsigned char *)workspace, L, st, fn);
     });
-    if (rc != RTK_OK) return rc;
-    return rtk_check_launch(fn);
 }
 
 }  // namespace

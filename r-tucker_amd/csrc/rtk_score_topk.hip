@@ -2,8 +2,8 @@
 // rows [col0, col0 + n_local) of O, exactly what rtk_select_topk_f32 gives on the probabilities of the stored score
 // kernels, with nothing of size batch x n_local in memory.
 //
-//   step 1  tmax_kernel    entity-stationary, the sweep of count_kernel (rtk_score_rank.hip): a workgroup of 4 waves keeps
-//                          128 converted rows of O as Frag B fragments and sweeps the query tiles through a
+//   step 1  tmax_kernel    entity-stationary, the sweep of rtk_score_rank_kernel.h: a workgroup of 4 waves keeps 128
+//                          converted rows of O as Frag B fragments and sweeps the query tiles through a
 //                          double-buffered LDS stage.  Each 32 x 32 tile of probabilities is reduced to its row maximum
 //                          over the tile's 128 entities -- over the 32 entity lanes by the halving butterfly, over the
 //                          4 waves through LDS -- and one float per (query, entity tile) goes to tmax (B, n_tiles).
@@ -37,35 +37,13 @@
 
 namespace {
 
-constexpr int TS_WAVES = 4;                    // waves per workgroup of the sweep: 128 entity rows per tile
-constexpr int TS_TILE = 32 * TS_WAVES;
-constexpr int TS_SLOTS = 2 * RTK_N_CU;         // resident workgroups of the sweep, two per CU
+constexpr int TS_WAVES = SW_WAVES;             // waves per workgroup of the sweep: 128 entity rows per tile
+constexpr int TS_TILE = SW_TILE;
 constexpr int TS_UQ = 4;                       // patch waves per query (one workgroup)
 constexpr int TS_KMAX = 128;
-constexpr int TS_MAX_KS_F32 = RTK_CG_MAX_KS;   // the ws kernel's range: c <= 208
-constexpr int TS_MAX_KS_BF16 = 32;             // score_bf16_kernel's range: c <= 512
 constexpr uint32_t TS_KEY_NINF = 0x007fffffu;  // sel_key(-inf): a masked or absent row
 
-// Maximum of v[0 .. 15] over the 32 lanes of a half wave, the exchange pattern of reduce16 (rtk_score_rank.hip):
-// afterwards lane r holds the maximum of element (r >> 1) & 15.
-template <int N, int O_>
-__device__ __forceinline__ void max_step(uint32_t (&v)[16], int r) {
-    const bool up = (r & O_) != 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        const uint32_t send = up ? v[i] : v[i + N];
-        const uint32_t keep = up ? v[i + N] : v[i];
-        v[i] = max(keep, (uint32_t)__shfl_xor((int)send, O_));
-    }
-}
-__device__ __forceinline__ uint32_t max16(uint32_t (&v)[16], int r) {
-    max_step<8, 16>(v, r);
-    max_step<4, 8>(v, r);
-    max_step<2, 4>(v, r);
-    max_step<1, 2>(v, r);
-    return max(v[0], (uint32_t)__shfl_xor((int)v[0], 1));
-}
-
+// LDS of tmax_kernel: two query tiles (nothing travels with them), then the waves' maxima
 template <typename T, int KS>
 struct MaxLds {
     static constexpr int TILE = (int)tile_bytes<T, KS>();
@@ -74,109 +52,67 @@ struct MaxLds {
     static constexpr int TOTAL = RED + 2 * RED_BUF;
 };
 
+// What tmax_kernel does with the sweep: the row maximum of each 32 x 32 tile of probabilities, on the select kernel's
+// keys, over the 32 entity lanes by the butterfly and over the 4 waves through LDS.
+template <typename T, int KS, int SG>
+struct MaxSweep {
+    typedef MaxLds<T, KS> L;
+    static constexpr int EXTRA = 0;
+    int B, n_tiles;
+    float *__restrict__ tmax;
+
+    __device__ __forceinline__ void load_extra(SweepLane, int) const {}
+    __device__ __forceinline__ void store_extra(SweepLane, int) const {}
+    __device__ __forceinline__ void begin_tile() const {}
+    __device__ __forceinline__ void end_tile(SweepLane, int) const {}
+    __device__ __forceinline__ void score(SweepLane ln, const Frag<T, KS> &f, const f32x16 &acc,
+                                          const unsigned char *buf, int cur, int, bool valid, int) const {
+        const int wave = ln.wave, r = ln.r, h = ln.h;
+        uint32_t key[16];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const int rw = acc_row(4 * g, h);
+            f32x4 sr4 = {1.f, 1.f, 1.f, 1.f};
+            if (Frag<T, KS>::PLANES == 2) sr4 = *reinterpret_cast<const f32x4 *>(buf + rw * 4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * g + q;
+                key[e] = valid ? sel_key(f.template prob<SG>(acc[e], sr4[q])) : TS_KEY_NINF;
+            }
+        }
+        const uint32_t m = reduce16(key, r, RedMax());
+        if (!(r & 1)) reinterpret_cast<uint32_t *>(sweep_lds + L::RED + cur * L::RED_BUF)[wave * 32 + red_row(r, h)] = m;
+    }
+    // query tile i of the range is written by wave i % TS_WAVES, the waves' maxima taken in wave order
+    __device__ __forceinline__ void publish(SweepLane ln, int cur, int i, int mt, int, int tile, bool) const {
+        const int wave = ln.wave, r = ln.r, h = ln.h;
+        if (wave == (i & (TS_WAVES - 1)) && h == 0) {
+            const int d = mt * 32 + r;
+            if (d < B) {
+                const uint32_t *rc = reinterpret_cast<const uint32_t *>(sweep_lds + L::RED + cur * L::RED_BUF);
+                const uint32_t s = max(max(rc[r], rc[32 + r]), max(rc[64 + r], rc[96 + r]));
+                tmax[(int64_t)d * n_tiles + tile] = sel_value(s, float());
+            }
+        }
+    }
+};
+
 // Step 1.  Workgroup (slot, qs): entity tiles slot, slot + n_slots, ...; query tiles of range qs.
 template <typename T, int KS, int SG>
 __global__ __launch_bounds__(64 * TS_WAVES, 2) void tmax_kernel(const unsigned char *__restrict__ qp, int B,
                                                                 const T *__restrict__ O, int n_local, int c, int n_slots,
                                                                 int qsplit, float *__restrict__ tmax, bool vec) {
-    typedef typename AFrag<T>::type AT;
-    typedef MaxLds<T, KS> L;
-    constexpr int NT = 64 * TS_WAVES;
-    constexpr int CHUNKS = L::TILE / 16;
-    constexpr int NLD = (CHUNKS + NT - 1) / NT;
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int slot = (int)blockIdx.x / qsplit, qs = (int)blockIdx.x % qsplit;
-    const int n_mt = (B + 31) >> 5, n_tiles = (n_local + TS_TILE - 1) / TS_TILE;
-    const int mt0 = (int)((int64_t)n_mt * qs / qsplit), nq = (int)((int64_t)n_mt * (qs + 1) / qsplit) - mt0;
-    if (nq <= 0 || slot >= n_tiles) return;                       // (never with the host's grid)
-
-    u32x4 stg[NLD];
-    auto stage_load = [&](int mt) {
-        const u32x4 *src = reinterpret_cast<const u32x4 *>(qp + (int64_t)mt * L::TILE);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int ch = i * NT + t;
-            if (i + 1 < NLD || ch < CHUNKS) stg[i] = src[ch];
-        }
-    };
-    auto stage_store = [&](int buf) {
-        u32x4 *dst = reinterpret_cast<u32x4 *>(lds + buf * L::TILE);
-#pragma unroll
-        for (int i = 0; i < NLD; ++i) {
-            const int ch = i * NT + t;
-            if (i + 1 < NLD || ch < CHUNKS) dst[ch] = stg[i];
-        }
-    };
-
-    stage_load(mt0);
-    int it = 0;                                                    // tiles staged so far: buffer parity
-    for (int tile = slot; tile < n_tiles; tile += n_slots) {
-        const int jl = tile * TS_TILE + wave * 32 + r;             // this lane's row of the block
-        const bool valid = jl < n_local;
-        Frag<T, KS> f;
-        f.load(O, min(jl, n_local - 1), c, h, vec);
-        f.template convert<SG>();
-        if (tile == slot) {
-            stage_store(0);
-            __syncthreads();
-        }
-        for (int i = 0; i < nq; ++i, ++it) {
-            const int cur = it & 1;
-            const bool more = i + 1 < nq || tile + n_slots < n_tiles;
-            if (more) stage_load(i + 1 < nq ? mt0 + i + 1 : mt0);
-            const unsigned char *buf = lds + cur * L::TILE;
-            const AT *la = reinterpret_cast<const AT *>(buf + RTK_PACK_HDR);
-            const f32x16 acc = f.chain_with([&](int plane, int ks) { return la[(plane * KS + ks) * 64 + lane]; });
-            // element e of the accumulator: query row 8 (e / 4) + 4 h + e % 4 of the tile, entity r of the wave
-            uint32_t key[16];
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const int rw = 8 * g + 4 * h;
-                f32x4 sr4 = {1.f, 1.f, 1.f, 1.f};
-                if (Frag<T, KS>::PLANES == 2) sr4 = *reinterpret_cast<const f32x4 *>(buf + rw * 4);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int e = 4 * g + q;
-                    key[e] = valid ? sel_key(f.template prob<SG>(acc[e], sr4[q])) : TS_KEY_NINF;
-                }
-            }
-            const uint32_t m = max16(key, r);
-            if (!(r & 1)) {
-                const int e = (r >> 1) & 15, rw = 8 * (e >> 2) + 4 * h + (e & 3);
-                reinterpret_cast<uint32_t *>(lds + L::RED + cur * L::RED_BUF)[wave * 32 + rw] = m;
-            }
-            if (more) stage_store(cur ^ 1);
-            __syncthreads();
-            // query tile i of the range is written by wave i % TS_WAVES, the waves' maxima taken in wave order
-            if (wave == (i & (TS_WAVES - 1)) && h == 0) {
-                const int d = (mt0 + i) * 32 + r;
-                if (d < B) {
-                    const uint32_t *rc = reinterpret_cast<const uint32_t *>(lds + L::RED + cur * L::RED_BUF);
-                    const uint32_t s = max(max(rc[r], rc[32 + r]), max(rc[64 + r], rc[96 + r]));
-                    tmax[(int64_t)d * n_tiles + tile] = sel_value(s, float());
-                }
-            }
-        }
-    }
+    MaxSweep<T, KS, SG> pol{B, (n_local + TS_TILE - 1) / TS_TILE, tmax};
+    sweep<T, KS, SG>(pol, qp, B, O, n_local, c, vec, n_slots, qsplit);
 }
 
-// One query against one entity tile, by one wave: the A fragments of query d in all 32 rows, so that element 0 of
-// lane r (h == 0) is the probability of entity row r of the 32 loaded ones.
+// One query against one entity tile, by one wave: QueryRow's scoring of the tile's four groups of 32 rows, and the
+// query's CSR segment as a mask on them.
 template <typename T, int KS, int SG>
-struct QueryTile {
-    typedef typename AFrag<T>::type AT;
-    AT A0[KS], A1[KS];
-    float srow;
+struct QueryTile : QueryRow<T, KS> {
     const int64_t *obj;                            // the query's CSR segment [e_lo, e_hi), global ids
     int64_t e_lo, e_hi, keep;
 
-    __device__ __forceinline__ void load(const unsigned char *__restrict__ qp, int d, int h) {
-        const int mt = d >> 5, row = d & 31;
-        load_a<T, KS>(qp, mt, row, h, A0, A1);
-        srow = Frag<T, KS>::PLANES == 2 ? reinterpret_cast<const float *>(qp + mt * tile_bytes<T, KS>())[row] : 1.0f;
-    }
     // the local tile of a CSR entry that takes part in the filter, else -1
     __device__ __forceinline__ int tile_of(int64_t jr, int col0, int n_local) const {
         const int64_t jl = jr - col0;
@@ -184,8 +120,8 @@ struct QueryTile {
     }
     // p[w], ok[w] of row tile * 128 + 32 w + r (meaningful in the lanes h == 0): the probability and whether the row
     // is in the block and not one of the query's filtered objects
-    __device__ __forceinline__ void score(const T *__restrict__ O, int n_local, int c, int col0, int tile, int lane, bool vec,
-                                          float (&p)[4], bool (&ok)[4]) const {
+    __device__ __forceinline__ void score_tile(const T *__restrict__ O, int n_local, int c, int col0, int tile, int lane,
+                                               bool vec, float (&p)[4], bool (&ok)[4]) const {
         const int r = lane & 31, h = lane >> 5;
         uint32_t m[4] = {0u, 0u, 0u, 0u};          // the tile's filtered rows, one bit each
         for (int64_t base = e_lo; base < e_hi; base += 64) {       // wave-uniform
@@ -211,10 +147,7 @@ struct QueryTile {
             ok[w] = false;
             if (tile * TS_TILE + 32 * w >= n_local) continue;      // wave-uniform: the block ends before these rows
             Frag<T, KS> f;
-            f.load(O, min(jl, n_local - 1), c, h, vec);
-            f.template convert<SG>();
-            const f32x16 acc = f.chain(A0, A1);
-            p[w] = f.template prob<SG>(acc[0], srow);
+            p[w] = this->template score<SG>(f, O, min(jl, n_local - 1), c, h, vec);
             ok[w] = jl < n_local && !((m[w] >> r) & 1u);
         }
     }
@@ -261,7 +194,7 @@ __global__ __launch_bounds__(64 * TS_UQ) void patch_kernel(const unsigned char *
                 }
                 float p[4];
                 bool ok[4];
-                q.score(O, n_local, c, col0, tile, lane, vec, p, ok);
+                q.score_tile(O, n_local, c, col0, tile, lane, vec, p, ok);
                 uint32_t m = TS_KEY_NINF;
 #pragma unroll
                 for (int w = 0; w < 4; ++w) m = max(m, ok[w] ? sel_key(p[w]) : TS_KEY_NINF);
@@ -325,7 +258,7 @@ __global__ __launch_bounds__(64 * TS_WAVES) void gather_kernel(const unsigned ch
     float p[4];
     bool ok[4];
     const int tile = (int)mine;
-    q.score(O, n_local, c, col0, tile, lane, vec, p, ok);
+    q.score_tile(O, n_local, c, col0, tile, lane, vec, p, ok);
     if (h == 0) {
 #pragma unroll
         for (int w = 0; w < 4; ++w) {
@@ -333,21 +266,6 @@ __global__ __launch_bounds__(64 * TS_WAVES) void gather_kernel(const unsigned ch
             cand_id[at + 32 * w + r] = ok[w] ? (int64_t)col0 + tile * TS_TILE + 32 * w + r : -1;
         }
     }
-}
-
-// workgroup slots and query ranges of the sweep: count_kernel's split (whole entity tiles per slot; with fewer tiles
-// than slots the query tiles are cut into ranges until the slots are used)
-struct SweepGrid {
-    int n_slots, qsplit;
-};
-SweepGrid grid_of(int64_t batch, int64_t n_local) {
-    const int64_t n_tiles = rtk_cdiv(n_local, TS_TILE), n_mt = rtk_cdiv(batch, 32);
-    SweepGrid g;
-    g.n_slots = (int)(n_tiles < TS_SLOTS ? n_tiles : TS_SLOTS);
-    int64_t q = TS_SLOTS / (g.n_slots > 0 ? g.n_slots : 1);
-    if (q > n_mt) q = n_mt;
-    g.qsplit = (int)(q < 1 ? 1 : q);
-    return g;
 }
 
 // [0, 256): the error word's header; the tile maxima; the selected tiles' values and ids; the candidates
@@ -371,19 +289,16 @@ TopkWs layout_of(int64_t batch, int64_t n_local, int k) {
 
 bool shape_ok(int dtype, int c, int k) {
     if (k < 1 || k > TS_KMAX || c < 1) return false;
-    if (dtype == RTK_F32) return c <= 16 * TS_MAX_KS_F32 && c % 4 == 0;
-    return dtype == RTK_BF16 && c <= 16 * TS_MAX_KS_BF16;
+    if (dtype == RTK_F32) return c <= 16 * SW_MAX_KS_F32 && c % 4 == 0;
+    return dtype == RTK_BF16 && c <= 16 * SW_MAX_KS_BF16;
 }
-
-template <typename T>
-bool vec_rows(const T *O, int c) { return sizeof(T) == 4 || (c % 8 == 0 && (reinterpret_cast<uintptr_t>(O) & 15) == 0); }
 
 template <typename T, int KS, int SG>
 int launch_topk(const unsigned char *qp, int B, const T *O, int n_local, int c, int col0, const int64_t *pair_slot,
                 const int64_t *pair_ptr, const int64_t *pair_obj, const int64_t *keep_idx, int k, float *values_out,
                 int64_t *ids_out, unsigned char *ws, hipStream_t st, const char *fn) {
     const TopkWs L = layout_of(B, n_local, k);
-    const SweepGrid g = grid_of(B, n_local);
+    const SweepGrid g = grid_of(B, n_local, SW_SLOTS);
     const int n_tiles = (int)L.n_tiles, k_t = (int)L.k_t;
     float *tmax = reinterpret_cast<float *>(ws + L.tmax);
     float *tval = reinterpret_cast<float *>(ws + L.tval);
@@ -392,18 +307,14 @@ int launch_topk(const unsigned char *qp, int B, const T *O, int n_local, int c, 
     int64_t *cid = reinterpret_cast<int64_t *>(ws + L.cid);
     const bool vec = vec_rows(O, c);
 
-    constexpr int bytes = MaxLds<T, KS>::TOTAL;
-    static std::atomic<unsigned long long> lds_ok{0};
-    if (bytes > 64 * 1024) {
-        const int rc = rtk_ensure_dynamic_lds(reinterpret_cast<const void *>(&tmax_kernel<T, KS, SG>), bytes, lds_ok, fn);
-        if (rc != RTK_OK) return rc;
-    }
-    RTK_LAUNCH_SCORE((tmax_kernel<T, KS, SG>), dim3((unsigned)(g.n_slots * g.qsplit)), dim3(64 * TS_WAVES), bytes, st, qp, B, O,
-                     n_local, c, g.n_slots, g.qsplit, tmax, vec);
+    int rc = launch_lds<&tmax_kernel<T, KS, SG>, MaxLds<T, KS>::TOTAL>(dim3((unsigned)(g.n_slots * g.qsplit)),
+                                                                       dim3(64 * TS_WAVES), st, fn, qp, B, O, n_local, c,
+                                                                       g.n_slots, g.qsplit, tmax, vec);
+    if (rc != RTK_OK) return rc;
     if (pair_slot)
         hipLaunchKernelGGL((patch_kernel<T, KS, SG>), dim3((unsigned)B), dim3(64 * TS_UQ), 0, st, qp, B, O, n_local, c, col0,
                            pair_slot, pair_ptr, pair_obj, keep_idx, tmax, vec);
-    int rc = rtk_check_launch(fn);
+    rc = rtk_check_launch(fn);
     if (rc != RTK_OK) return rc;
     rc = rtk_select_topk_f32(tmax, B, n_tiles, n_tiles, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, k_t, tval, tid,
                              nullptr, 0, st);
@@ -422,44 +333,21 @@ int score_topk(const char *fn, const void *q_packed, int64_t batch, int c, const
                int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
                const int64_t *keep_idx, int k, unsigned flags, float *values_out, int64_t *ids_out, void *workspace,
                size_t ws_bytes, void *stream) {
-    constexpr bool F32 = sizeof(T) == 4;
-    RTK_REQUIRE(q_packed && O && values_out && ids_out && workspace, RTK_ERR_BAD_ARG, "%s: null operand", fn);
-    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "%s: pair_slot without the CSR arrays", fn);
-    RTK_REQUIRE(batch >= 0, RTK_ERR_BAD_ARG, "%s: batch = %lld must be >= 0", fn, (long long)batch);
-    RTK_REQUIRE(n_ent >= 1, RTK_ERR_BAD_ARG, "%s: n_ent = %lld must be >= 1", fn, (long long)n_ent);
-    RTK_REQUIRE(col0 >= 0 && n_local >= 1 && n_local <= n_ent && col0 <= n_ent - n_local, RTK_ERR_BAD_ARG,
-                "%s: block col0 = %lld, n_local = %lld is not a non-empty part of [0, n_ent = %lld)", fn, (long long)col0,
-                (long long)n_local, (long long)n_ent);
-    RTK_REQUIRE(c >= 1, RTK_ERR_BAD_ARG, "%s: object rank c = %d must be >= 1", fn, c);
-    RTK_REQUIRE(k >= 1 && k <= TS_KMAX, RTK_ERR_BAD_ARG, "%s: k = %d outside [1, %d]", fn, k, TS_KMAX);
-    RTK_REQUIRE(batch < (1ll << 31) - 32 && n_ent < (1ll << 31) - 256, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
-    RTK_REQUIRE(batch * (int64_t)TS_KMAX < (1ll << 31), RTK_ERR_UNSUPPORTED,
-                "%s: batch = %lld too large for one call (split the queries)", fn, (long long)batch);
-    RTK_REQUIRE(flags & RTK_SCORE_SIGMOID, RTK_ERR_UNSUPPORTED,
-                "%s: the top k is taken on probabilities: flags need RTK_SCORE_SIGMOID (raw logits are not covered)", fn);
-    RTK_REQUIRE((flags & ~(RTK_SCORE_SIGMOID | RTK_SCORE_SIGMOID_FAST)) == 0, RTK_ERR_BAD_ARG, "%s: unknown flags 0x%x",
-                fn, flags);
-    if (F32) {
-        RTK_REQUIRE(c <= 16 * TS_MAX_KS_F32, RTK_ERR_UNSUPPORTED, "%s: c = %d above %d (the ws kernel's range)", fn, c,
-                    16 * TS_MAX_KS_F32);
-        RTK_REQUIRE(c % 4 == 0 && (reinterpret_cast<uintptr_t>(O) & 15) == 0, RTK_ERR_UNSUPPORTED,
-                    "%s: fp32 needs c %% 4 == 0 and a 16-byte-aligned O (c = %d)", fn, c);
-    } else {
-        RTK_REQUIRE(c <= 16 * TS_MAX_KS_BF16, RTK_ERR_UNSUPPORTED, "%s: c = %d above %d", fn, c, 16 * TS_MAX_KS_BF16);
-    }
-    const size_t need = layout_of(batch, n_local, k).total;
-    RTK_REQUIRE(ws_bytes >= need, RTK_ERR_BAD_ARG, "%s: workspace of %zu bytes given, %zu needed", fn, ws_bytes, need);
-    RTK_REQUIRE((reinterpret_cast<uintptr_t>(workspace) & 255) == 0, RTK_ERR_BAD_ARG, "%s: workspace must be 256-byte aligned",
-                fn);
-    if (batch == 0) return RTK_OK;
-    const bool fast = (flags & RTK_SCORE_SIGMOID_FAST) != 0;
-    return rtk_dispatch_ksteps<F32 ? TS_MAX_KS_F32 : TS_MAX_KS_BF16>((c + 15) / 16, fn, [&](auto K) {
-        auto go = [&](auto SG) {
-            return launch_topk<T, K.value, SG.value>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c, (int)col0,
-                                                     pair_slot, pair_ptr, pair_obj, keep_idx, k, values_out, ids_out,
-                                                     (unsigned char *)workspace, (hipStream_t)stream, fn);
-        };
-        return fast ? go(std::integral_constant<int, 2>{}) : go(std::integral_constant<int, 1>{});
+    const auto own = [&]() -> int {
+        RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "%s: pair_slot without the CSR arrays", fn);
+        RTK_REQUIRE(k >= 1 && k <= TS_KMAX, RTK_ERR_BAD_ARG, "%s: k = %d outside [1, %d]", fn, k, TS_KMAX);
+        RTK_REQUIRE(batch * (int64_t)TS_KMAX < (1ll << 31), RTK_ERR_UNSUPPORTED,
+                    "%s: batch = %lld too large for one call (split the queries)", fn, (long long)batch);
+        return RTK_OK;
+    };
+    const int rc = check_block(fn, q_packed && values_out && ids_out, batch, c, O, n_local, col0, n_ent, own,
+                               (1ll << 31) - 256, flags, "the top k is", workspace, ws_bytes,
+                               [&] { return layout_of(batch, n_local, k).total; });
+    if (rc != RTK_OK || batch == 0) return rc;
+    return dispatch<T>(fn, c, flags, [&](auto K, auto SG) {
+        return launch_topk<T, K.value, SG.value>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c, (int)col0,
+                                                 pair_slot, pair_ptr, pair_obj, keep_idx, k, values_out, ids_out,
+                                                 (unsigned char *)workspace, (hipStream_t)stream, fn);
     });
 }
 

@@ -1057,6 +1057,24 @@ def rank_targets_block(qp, B, O_loc, col0, n_ent, object_idx, sigmoid_mode=None)
     return pt
 
 
+def _block_filter(b, flt, slots, keep_idx=None):
+    """``(slots, keep_idx)`` of a block call as int64 index tensors on the block's device, one entry per query (None
+    stays None); ``slots`` go with ``flt``, the ``DeviceFilter`` that holds the CSR."""
+    if flt is not None:
+        if slots is None:
+            raise ValueError("filtering needs the queries' filter slots: slots=flt.slots_of(subject_idx, relation_idx)")
+        slots = _idx("slots", slots, b.dev)
+        if slots.numel() != b.B:
+            raise RuntimeError(f"slots has {slots.numel()} entries for {b.B} queries")
+    elif slots is not None:
+        raise ValueError("slots need flt (the DeviceFilter that holds the CSR)")
+    if keep_idx is not None:
+        keep_idx = _idx("keep_idx", keep_idx, b.dev)
+        if keep_idx.numel() != b.B:
+            raise RuntimeError(f"keep_idx has {keep_idx.numel()} entries for {b.B} queries")
+    return slots, keep_idx
+
+
 @torch.no_grad()
 def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, slots=None, want_bce=False,
                           sigmoid_mode=None):
@@ -1070,14 +1088,7 @@ def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, s
     if (not isinstance(pt, torch.Tensor) or pt.dtype != torch.float32 or pt.device != b.dev or pt.numel() != b.B):
         raise RuntimeError(f"pt must be a float32 tensor of {b.B} target scores on {b.dev}")
     pt = pt.contiguous().view(-1)
-    if flt is not None:
-        if slots is None:
-            raise ValueError("filtering needs the queries' filter slots: slots=flt.slots_of(subject_idx, relation_idx)")
-        slots = _idx("slots", slots, b.dev)
-        if slots.numel() != b.B:
-            raise RuntimeError(f"slots has {slots.numel()} entries for {b.B} queries")
-    elif slots is not None:
-        raise ValueError("slots need flt (the DeviceFilter that holds the CSR)")
+    slots, _ = _block_filter(b, flt, slots)
     counts = torch.empty(b.B, dtype=torch.int32, device=b.dev)
     bce = torch.empty(b.B, dtype=torch.float64, device=b.dev) if want_bce else None
     if b.B == 0:
@@ -1132,18 +1143,7 @@ def topk_block_1vN(qp, B, O_loc, col0, n_ent, k, flt=None, slots=None, keep_idx=
     _check_topk_stream_k(k)
     b = _Block(qp, B, O_loc, col0, n_ent, None)
     flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
-    if flt is not None:
-        if slots is None:
-            raise ValueError("filtering needs the queries' filter slots: slots=flt.slots_of(subject_idx, relation_idx)")
-        slots = _idx("slots", slots, b.dev)
-        if slots.numel() != b.B:
-            raise RuntimeError(f"slots has {slots.numel()} entries for {b.B} queries")
-    elif slots is not None:
-        raise ValueError("slots need flt (the DeviceFilter that holds the CSR)")
-    if keep_idx is not None:
-        keep_idx = _idx("keep_idx", keep_idx, b.dev)
-        if keep_idx.numel() != b.B:
-            raise RuntimeError(f"keep_idx has {keep_idx.numel()} entries for {b.B} queries")
+    slots, keep_idx = _block_filter(b, flt, slots, keep_idx)
     if _size("rtk_score_topk_workspace_bytes", b.dcode, max(b.B, 1), b.n_loc, b.c, k) == 0:
         raise RuntimeError(f"topk_block_1vN: object rank c = {b.c} is not covered (float32: c <= 208 and c % 4 == 0; "
                            "bfloat16: c <= 512); there is no fallback")
