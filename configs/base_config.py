@@ -6,7 +6,9 @@ configurations (``README.md:36-45``): the shipped defaults do NOT encode them (S
 
 New fields (not in the reference): ``TrainConfig.scheduler`` -- ``"onecycle"`` is what ``train.py:213-215``
 hard-codes (OneCycleLR, max_lr 600, ignoring ``learning_rate``), ``"exp"`` is the README's ``lr`` /
-``lr_decay`` column (``learning_rate`` decayed by ``scheduler_step`` per epoch); ``LogConfig.use_wandb``.
+``lr_decay`` column (``learning_rate`` decayed by ``scheduler_step`` per epoch); ``LogConfig.use_wandb``;
+``TrainConfig.loss`` -- ``"bce"`` is the reference's ``nn.BCELoss`` on sigmoid scores, ``"ce"`` the softmax
+cross-entropy over the entities (``ops.ce_loss_1vN``).
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ class TrainConfig(_Dictable):
     learning_rate: float = 2000
     scheduler_step: float = 0.995
     scheduler: str = "onecycle"
+    loss: str = "bce"                # "ce": softmax cross-entropy over the entities (ops.ce_loss_1vN)
 
     base_regularization_coeff: float = 1e-11
     final_regularization_coeff: float = 1e-16

@@ -769,6 +769,75 @@ int rtk_bce_stream_grad_o_part_f32(const void *q_packed, const float *v, int64_t
                                    float label_smoothing, unsigned flags, const float *scale, float *gO_local_out,
                                    void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * The 1-vs-all softmax cross-entropy training loss, the other standard loss of 1-vs-all link prediction: what a user
+ * of the reference gets by replacing criterion = nn.BCELoss (train.py:76-82, :136) on sigmoid scores with
+ * torch.nn.functional.cross_entropy on the logits, the targets of src/data/Dataset.py:43-53 normalised per row.  For
+ * batch item d let P_d be the CSR list of its pair (every object once), n_d = |P_d|, N = n_ent, eps the smoothing:
+ *     y[d, j]  = (1 - eps) [j in P_d] / n_d + eps / N          (first term absent when n_d = 0)
+ *     w_d      = sum_j y[d, j] = (1 - eps) [n_d > 0] + eps
+ *     lse_d    = log sum_j exp(z[d, j])                         (row maximum subtracted)
+ *     loss     = (1 / B) sum_d ( w_d lse_d - sum_j y[d, j] z[d, j] )  = F.cross_entropy(z, y), mean reduction
+ *     d loss / d z[d, j] = (w_d softmax(z_d)_j - y[d, j]) / B   (every column: there is no saturation rule)
+ * pair_slot[d] < 0 is an empty list; entries outside [0, n_ent) are skipped.
+ *
+ * Matrix form (rtk_ce.hip), on STORED fp32 logits Z (batch x n_ent, row pitch ld; any c -- what
+ * rtk_score_*(flags without RTK_SCORE_SIGMOID) wrote):
+ *   rtk_ce_rows_f32  one pass per row: lse_out[d] (float) and rows_out[d] = w_d lse_d - sum_j y z (float64
+ *                    accumulation across groups of eight columns; loss = sum(rows_out) / batch)
+ *   rtk_ce_grad_f32  in place  Z[d, j] <- (w_d exp(Z[d, j] - lse[d]) - y[d, j]) * grad_loss[0] * scale; with
+ *                    scale = 1 / batch this is d loss / d logits, |.| <= |g| / batch, the left operand of the dO / dv
+ *                    GEMMs.  grad_loss is a DEVICE scalar.
+ */
+int rtk_ce_rows_f32(const float *Z, int64_t batch, int64_t n_ent, int64_t ld, const int64_t *pair_slot,
+                    const int64_t *pair_ptr, const int64_t *pair_obj, float label_smoothing, double *rows_out,
+                    float *lse_out, void *stream);
+int rtk_ce_grad_f32(float *Z, int64_t batch, int64_t n_ent, int64_t ld, const int64_t *pair_slot,
+                    const int64_t *pair_ptr, const int64_t *pair_obj, float label_smoothing, const float *lse,
+                    const float *grad_loss, float scale, void *stream);
+
+/*
+ * The same loss WITHOUT the (batch x n_ent) logit matrix (rtk_ce_stream.hip): the sweeps of rtk_bce_stream_* with the
+ * softmax link.  z[d, j] is the accumulated value of the ws score kernel's split-fp16 chain times its row and column
+ * factors, acc * srow * 2^-sh: the logit of rtk_score_rank_f32 / rtk_bce_stream_*, without the logistic.
+ *   rtk_ce_stream_rows_f32  the forward, ONE sweep and no second tile product: every lane keeps an online (maximum, sum
+ *                           of exp) and the sum of z of its query over its 16 entities per 32-row entity tile (columns
+ *                           past n_ent: -inf for the lse, 0 for the sum); the partials of the `splits` entity ranges
+ *                           are merged in range order in float64; the positives' term -(1 - eps) / n_d sum_{t in P_d} z_t
+ *                           comes from re-scoring the CSR entries with the same chain.  loss_rows_out[d] (float64;
+ *                           loss = sum / batch) and lse_out[d] (float).
+ *   rtk_ce_stream_grad_f32  the backward, from lse: with x[d, j] = w_d exp(z[d, j] - lse[d]) - eps / N (|x| <= 1) and
+ *                           the positives as the constant -(1 - eps) / n_d per CSR entry,
+ *                             dv_out[d, :] = sum_j x[d, j] O[j, :]               (batch x c, UNSCALED: multiply by g / batch
+ *                                                                              before rtk_query_vectors_bwd_f32), and
+ *                             gO_out[j, :] = sum_d x[d, j] scale[0] v[d, :]      (all n_ent x c written; scale: one float
+ *                                                                              on the device, g / batch).
+ *                           Either output may be NULL: its sweep is skipped (v and scale are needed for gO_out only).
+ * Tile products, summation orders, max_pos and the error word as rtk_bce_stream_*: sweep 1 cuts the entity tiles into
+ * `splits` = max(1, 256 / ceil(batch / 128)) ranges, added in range order; sweep 2 adds the query tiles in increasing
+ * order onto the positives' share from the ordered scatter; the tile's 32 values of lse and w travel with the query tile.
+ * No float atomics, repeated calls give the same bits, nothing grows with batch * n_ent.  A row with w_d = 0 (eps = 0 and
+ * an empty list) contributes nothing.
+ * Workspace: rtk_ce_stream_workspace_bytes(batch, n_ent, c, max_pos) (rows: max_pos = 0), valid without a device,
+ * 256-byte aligned, first word the error word; with cp = 32 * ceil(c / 32), S = splits:
+ *     512 + align256(4 S batch) + 2 align256(8 S batch) + align256(32 batch) + align256(4 S batch cp)
+ *         + 2 align256(4 batch c) + align256(128 cp ceil(batch / 32)) + align256(256 ceil(batch / 32))
+ *         + align256(4 (batch + 1)) + 3 align256(4 max_pos) + rtk_score_candidates_bwd_workspace_bytes(max_pos, 1, .).
+ * Covered shapes: fp32, c <= 208, c % 4 == 0, 16-byte-aligned O; others give RTK_ERR_UNSUPPORTED (no fallback to the
+ * matrix form).  RTK_ERR_BAD_ARG before anything is enqueued: null pointers, negative sizes, label smoothing outside
+ * [0, 1), a workspace too small or misaligned.  batch == 0: rows returns at once, grad zeroes gO_out.  Static launch
+ * sequences on `stream`, no host synchronisation; graph-capturable.
+ */
+size_t rtk_ce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos);
+int rtk_ce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                           const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                           float label_smoothing, double *loss_rows_out, float *lse_out, void *workspace,
+                           size_t ws_bytes, void *stream);
+int rtk_ce_stream_grad_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O, int64_t n_ent,
+                           const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                           int64_t max_pos, float label_smoothing, const float *lse, const float *scale,
+                           float *dv_out, float *gO_out, void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,9 @@
 //
 //     x[d, j] = p[d, j] - eps / N        (0 where the fp32 p is exactly 1.0f or 0.0f),
 //
-// and the positives (the CSR entries, whose target is eps / N + (1 - eps)) are a sparse correction:
+// and the positives (the CSR entries, whose target is eps / N + (1 - eps)) are a sparse correction.  The skeletons of
+// the three kernels are rtk_stream_kernel.h's (rows_sweep, GoSweep / go_kernel, pos_kernel), shared with the softmax
+// cross-entropy loss (rtk_ce_stream.hip); this file holds the BCE link functions (BceRows, BceGo, BcePos) and the host:
 //
 //   rows_kernel   sweep 1.  The score tile is computed with the QUERY on the lane and the entities in the accumulator
 //                 registers (entity fragments as the A operand, the packed query planes as B), so the 32 x 32 tile of x is
@@ -29,221 +31,54 @@
 //
 // Both tile products are three f16 MFMAs per k-step on hi/lo halves (x scaled by 2^14; O and s v by a power of two from
 // their largest magnitude), accumulated in fp32.  No float atomics: every sum has a fixed order.
-#include "rtk_common.h"
-#include "rtk_pack.h"
-#include "rtk_score_rank_kernel.h"
-#include "rtk_score_select.h"
-
-// the flat front end of the ordered scatter (rtk_candidates.hip)
-size_t rtk_cand_flat_workspace_bytes(int64_t m);
-int rtk_cand_flat_scatter(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m,
-                          int64_t n_ent, const float *v, int c, float *gO, void *workspace, hipStream_t st);
+#include "rtk_stream_kernel.h"
 
 namespace {
-
-constexpr int BS_WAVES = SW_WAVES;
-constexpr int BS_MAX_KS = SW_MAX_KS_F32;       // Frag<float, KS>'s range: c <= 208
-constexpr int BS_POS_Y = 4;                    // loss partials per query of pos_kernel (one per wave)
-constexpr float BS_X_UP = 16384.0f;            // |x| <= 1 scaled to 2^14 before the hi/lo split
-
-__host__ __device__ constexpr int nct_of(int ks) { return (ks + 1) / 2; }       // 32-column tiles of 16 ks columns
-// bytes of the transposed image of a 32-row tile: [plane][column tile][k-step][lane][8 halves]
-__host__ __device__ constexpr int timg_bytes(int ks) { return nct_of(ks) * 4096; }
-
-// index, in halves, of element (row j of the tile, column col) in plane 0 of the transposed image: lane (col & 31, h)
-// holds in k-step t the rows 16 t + 8 (q >> 2) + 4 h + (q & 3), q = 0..7 -- the order in which an accumulator tile
-// supplies its rows as an operand
-__device__ __forceinline__ int timg_index(int j, int col) {
-    const int t = j >> 4, q = ((j >> 3) & 1) * 4 + (j & 3), h = (j >> 2) & 1;
-    return ((((col >> 5) * 2 + t) * 64) + h * 32 + (col & 31)) * 8 + q;
-}
-
-__device__ __forceinline__ f32x16 zero16() {
-    return f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-}
 
 // x of one probability and its BCE term as a negative
 __device__ __forceinline__ float x_of(float p, float t0, bool valid) {
     return (valid && p != 1.0f && p != 0.0f) ? p - t0 : 0.0f;
 }
 
-// the 16 values of a tile held by a lane, scaled and split into the two k-steps' operand fragments
-__device__ __forceinline__ void split_x(const float (&x)[16], f16x8 (&xh)[2], f16x8 (&xl)[2]) {
+// sweep 1's link: the BCE terms of the tile summed per query, x = p - eps / N
+template <int KS, int SG>
+struct BceRows {
+    float t0;
+    double *__restrict__ part_loss;
+    double lsum;
+    __device__ __forceinline__ void begin(int, bool) { lsum = 0.0; }
+    __device__ __forceinline__ void tile(const f32x16 &acc, float srow, const unsigned char *kc, int tile, int h, int N,
+                                         float (&x)[16]) {
+        float ls = 0.f;
 #pragma unroll
-    for (int t = 0; t < 2; ++t)
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 kc4 = *reinterpret_cast<const f32x4 *>(kc + (8 * g + 4 * h) * 4);
 #pragma unroll
-        for (int q = 0; q < 8; ++q) {
-            const float y = x[8 * t + q] * BS_X_UP;
-            const _Float16 hi = (_Float16)y;
-            xh[t][q] = hi;
-            xl[t][q] = (_Float16)(y - (float)hi);
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * g + q;
+                const bool valid = tile * 32 + 8 * g + 4 * h + q < N;
+                const float p = Frag<float, KS>::template logistic<SG>(acc[e], srow, kc4[q]);
+                x[e] = x_of(p, t0, valid);
+                ls += valid ? t0 * rtk_clog(p) + (1.0f - t0) * rtk_clog(1.0f - p) : 0.f;
+            }
         }
-}
-
-// acc[ct] += X * T for the transposed image `timg` (plane stride in 16-byte units: NCT * 128)
-template <int NCT>
-__device__ __forceinline__ void tile_product(const f16x8 (&xh)[2], const f16x8 (&xl)[2], const f16x8 *__restrict__ timg,
-                                             int lane, f32x16 (&acc)[NCT]) {
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            const f16x8 bh = timg[(ct * 2 + t) * 64 + lane], bl = timg[(NCT * 2 + ct * 2 + t) * 64 + lane];
-            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[t], bh, acc[ct], 0, 0, 0);
-            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xh[t], bl, acc[ct], 0, 0, 0);
-            acc[ct] = __builtin_amdgcn_mfma_f32_32x32x16_f16(xl[t], bh, acc[ct], 0, 0, 0);
-        }
-}
-
-template <int KS>
-struct RowsLds {
-    static constexpr int NCT = nct_of(KS);
-    static constexpr int A1 = 0;                       // [2][KS][64] x 16 B: the tile's rows as the chain's operand
-    static constexpr int T2 = 2 * KS * 1024;           // the transposed image of the same rows (one scale for all of O)
-    static constexpr int KC = T2 + timg_bytes(KS);     // 32 floats: Frag's kcol of the rows
-    static constexpr int TOTAL = KC + 128;
+        lsum += (double)ls;
+    }
+    __device__ __forceinline__ void finish(int sp, int d, int h, int B) {
+        lsum += __shfl_xor(lsum, 32);
+        if (h == 0 && d < B) part_loss[(int64_t)sp * B + d] = lsum;
+    }
 };
 
-// Sweep 1.  Workgroup (qg, sp): query tiles 4 qg .. 4 qg + 3 (one per wave), entity tiles of split sp.
+// Sweep 1 (rows_sweep) with the BCE link.
 template <int KS, int SG, bool DV>
 __global__ __launch_bounds__(64 * BS_WAVES, 1) void rows_kernel(const unsigned char *__restrict__ qp, int B,
                                                                 const float *__restrict__ O, int N, int c, float t0,
                                                                 const float *__restrict__ o_bound, int n_splits,
                                                                 double *__restrict__ part_loss,
                                                                 float *__restrict__ slab) {
-    typedef RowsLds<KS> L;
-    constexpr int NCT = L::NCT, CP = 32 * NCT;
-    constexpr int NF = (4 * KS + 7) / 8;               // float4 pieces of a row per staging thread
-    extern __shared__ __attribute__((aligned(16))) unsigned char lds[];
-
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6, r = lane & 31, h = lane >> 5;
-    const int qg = (int)blockIdx.x / n_splits, sp = (int)blockIdx.x % n_splits;
-    const int n_mt = (B + 31) >> 5, n_t = (N + 31) >> 5;
-    const int mt = qg * BS_WAVES + wave;
-    const bool active = mt < n_mt;                                  // (wave-uniform)
-    const int tb = (int)((int64_t)n_t * sp / n_splits), te = (int)((int64_t)n_t * (sp + 1) / n_splits);
-
-    f16x8 Qh[KS], Ql[KS];
-    float srow = 1.0f;
-    if (active) {
-        load_a<float, KS>(qp, mt, r, h, Qh, Ql);
-        srow = reinterpret_cast<const float *>(qp + mt * tile_bytes<float, KS>())[r];
-    } else {
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) Qh[ks] = Ql[ks] = f16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
-    f32x16 dacc[NCT];
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct) dacc[ct] = zero16();
-    double lsum = 0.0;
-    const float up2 = DV ? ldexpf(1.0f, rtk_pack_shift(o_bound[0])) : 1.0f;
-
-    // staging: 8 consecutive threads take one row, thread `part` the float4 pieces part, part + 8, ...
-    const int srw = t >> 3, part = t & 7;
-    f32x4 stg[NF];
-    auto stage_load = [&](int tile) {
-        const float *row = O + (int64_t)min(tile * 32 + srw, N - 1) * c;
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            const int k0 = 4 * (part + 8 * i);
-            stg[i] = (k0 + 4 <= c) ? *reinterpret_cast<const f32x4 *>(row + k0) : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-    };
-    auto stage_store = [&]() {
-        float mx = 0.f;
-#pragma unroll
-        for (int i = 0; i < NF; ++i)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) mx = fmaxf(mx, fabsf(stg[i][q]));
-        mx = fmaxf(mx, __shfl_xor(mx, 1));
-        mx = fmaxf(mx, __shfl_xor(mx, 2));
-        mx = fmaxf(mx, __shfl_xor(mx, 4));
-        float up, kc;
-        Frag<float, KS>::template row_scale<SG>(mx, up, kc);
-        if (part == 0) reinterpret_cast<float *>(lds + L::KC)[srw] = kc;
-        _Float16 *t2 = reinterpret_cast<_Float16 *>(lds + L::T2);
-#pragma unroll
-        for (int i = 0; i < NF; ++i) {
-            const int f = part + 8 * i;
-            if (f >= 4 * KS) continue;
-            const int ks = f >> 2, hh = (f >> 1) & 1, q0 = (f & 1) * 4;
-            f16x4 hi, lo;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float y = stg[i][q] * up;
-                const _Float16 y0 = (_Float16)y;
-                hi[q] = y0;
-                lo[q] = (_Float16)(y - (float)y0);
-            }
-            const int at = (ks * 64 + hh * 32 + srw) * 16 + q0 * 2;
-            *reinterpret_cast<f16x4 *>(lds + L::A1 + at) = hi;
-            *reinterpret_cast<f16x4 *>(lds + L::A1 + KS * 1024 + at) = lo;
-            if (DV) {                                               // (columns past 16 KS stay unwritten: they feed output columns >= c, never stored)
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const float y = stg[i][q] * up2;
-                    const _Float16 y0 = (_Float16)y;
-                    const int ix = timg_index(srw, 4 * f + q);
-                    t2[ix] = y0;
-                    t2[NCT * 1024 + ix] = (_Float16)(y - (float)y0);
-                }
-            }
-        }
-    };
-
-    if (tb < te) stage_load(tb);
-    for (int tile = tb; tile < te; ++tile) {
-        stage_store();
-        __syncthreads();
-        if (tile + 1 < te) stage_load(tile + 1);
-        if (active) {
-            const f16x8 *la = reinterpret_cast<const f16x8 *>(lds + L::A1);
-            f32x16 acc;
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {                       // Frag::chain's products with the roles swapped
-                const f16x8 eh = la[ks * 64 + lane], el = la[(KS + ks) * 64 + lane];
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(eh, Qh[ks], ks == 0 ? zero16() : acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(el, Qh[ks], acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(eh, Ql[ks], acc, 0, 0, 0);
-            }
-            // element e: entity row 8 (e / 4) + 4 h + e % 4 of the tile, query r of the wave
-            float x[16];
-            float ls = 0.f;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) {
-                const f32x4 kc4 = *reinterpret_cast<const f32x4 *>(lds + L::KC + (8 * g + 4 * h) * 4);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const int e = 4 * g + q;
-                    const bool valid = tile * 32 + 8 * g + 4 * h + q < N;
-                    const float p = Frag<float, KS>::template logistic<SG>(acc[e], srow, kc4[q]);
-                    x[e] = x_of(p, t0, valid);
-                    ls += valid ? t0 * rtk_clog(p) + (1.0f - t0) * rtk_clog(1.0f - p) : 0.f;
-                }
-            }
-            lsum += (double)ls;
-            if (DV) {
-                f16x8 xh[2], xl[2];
-                split_x(x, xh, xl);
-                tile_product<NCT>(xh, xl, reinterpret_cast<const f16x8 *>(lds + L::T2), lane, dacc);
-            }
-        }
-        __syncthreads();
-    }
-    if (!active) return;
-    lsum += __shfl_xor(lsum, 32);
-    const int d = mt * 32 + r;
-    if (h == 0 && d < B) part_loss[(int64_t)sp * B + d] = lsum;
-    if (DV) {
-        // element e of dacc[ct]: query row 8 (e / 4) + 4 h + e % 4 of the tile, column 32 ct + r
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int dq = mt * 32 + acc_row(e, h);
-                if (dq < B) slab[((int64_t)sp * B + dq) * CP + ct * 32 + r] = dacc[ct][e];
-            }
-    }
+    BceRows<KS, SG> pol{t0, part_loss, 0.0};
+    rows_sweep<KS, SG, DV>(pol, qp, B, O, N, c, o_bound, n_splits, slab);
 }
 
 // loss_rows[d] = -(the splits' partial sums, in split order) + the positives' correction;
@@ -263,250 +98,33 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(int B, int c, int cp, 
         for (int u = 0; u < BS_POS_Y; ++u) pcor += rows_pos[(int64_t)d * BS_POS_Y + u];
         loss_rows[d] = -s + pcor;
     }
-    if (dv && t < c) {
-        const float un = ldexpf(1.0f, -14 - rtk_pack_shift(o_bound[0]));
-        float s = 0.f;
-        for (int k = 0; k < n_splits; ++k) s += slab[((int64_t)k * B + d) * cp + t];
-        dv[(int64_t)d * c + t] = s * un + dvpos[(int64_t)d * c + t];
-    }
+    finish_dv_row(d, t, B, c, cp, n_splits, slab, dvpos, o_bound, dv);
 }
 
-// off[d] = entries of the queries before d in the flat lists (exclusive prefix of the CSR list lengths), off[B] = all.
-__global__ __launch_bounds__(256) void pos_offsets_kernel(int B, const int64_t *__restrict__ pair_slot,
-                                                          const int64_t *__restrict__ pair_ptr, int64_t max_pos,
-                                                          int32_t *__restrict__ off, uint32_t *__restrict__ err) {
-    __shared__ long long wsum[4];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    long long carry = 0;
-    for (int b0 = 0; b0 < B; b0 += 256) {
-        const int d = b0 + t;
-        long long len = 0;
-        if (d < B) {
-            const int64_t s = pair_slot[d];
-            if (s >= 0) len = pair_ptr[s + 1] - pair_ptr[s];
-            if (len < 0) len = 0;
-        }
-        long long inc = len;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long long y = __shfl_up(inc, o);
-            if (lane >= o) inc += y;
-        }
-        if (lane == 63) wsum[wv] = inc;
-        __syncthreads();
-        long long before = 0, tot = 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            before += i < wv ? wsum[i] : 0;
-            tot += wsum[i];
-        }
-        __syncthreads();
-        const long long ex = carry + before + inc - len;
-        if (d < B) off[d] = (int32_t)(ex < max_pos ? ex : max_pos);
-        carry += tot;
-    }
-    if (t == 0) {
-        off[B] = (int32_t)(carry < max_pos ? carry : max_pos);
-        if (carry > max_pos) atomicOr(err, 8u);                   // the lists are longer than the caller's bound
-    }
-}
-
-__global__ __launch_bounds__(256) void pos_fill_kernel(int64_t m, int32_t n_ent, int32_t *__restrict__ ent,
-                                                       int32_t *__restrict__ owner, float *__restrict__ dzf) {
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < m; i += (int64_t)gridDim.x * 256) {
-        ent[i] = n_ent;                                           // no entity: adds nothing
-        owner[i] = 0;
-        dzf[i] = 0.f;
-    }
-}
-
-// The positives of query d = blockIdx.x: wave w takes the CSR entries [i0 + 32 (w + 4 k), + 32), one per column of a
-// tile whose rows are all query d (filter_kernel's form).  pair_obj holds global ids; the block owns col0 <= id < col0 + N
-// (local row id - col0), every other entry is skipped.
-template <int KS, int SG>
-__global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char *__restrict__ qp, int B,
-                                                            const float *__restrict__ O, int N, int col0, int c, float dt,
-                                                            const int64_t *__restrict__ pair_slot,
-                                                            const int64_t *__restrict__ pair_ptr,
-                                                            const int64_t *__restrict__ pair_obj,
-                                                            double *__restrict__ rows_pos, float *__restrict__ dvpos,
-                                                            const int32_t *__restrict__ off, int64_t max_pos,
-                                                            int32_t *__restrict__ ent, int32_t *__restrict__ owner,
-                                                            float *__restrict__ dzf) {
-    __shared__ float part[BS_WAVES][256];
-    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
-    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int d = blockIdx.x;
-    const int64_t s = pair_slot[d];
-    const int64_t i0 = s >= 0 ? pair_ptr[s] : 0, i1 = s >= 0 ? pair_ptr[s + 1] : 0;
-    float lacc = 0.f;
-    float dva[4] = {0.f, 0.f, 0.f, 0.f};
-    if (i0 + 32 * wave < i1) {
-        QueryRow<float, KS> q;
-        q.load(qp, d, h);
-        Frag<float, KS> f;
-        for (int64_t base = i0 + 32 * wave; base < i1; base += 32 * BS_WAVES) {       // wave-uniform
-            const int64_t i = base + r;
-            const int64_t jr = i < i1 ? pair_obj[i] - col0 : -1;     // local row
-            const bool ok = jr >= 0 && jr < N;
-            float dz = 0.f;
-            if (__ballot(ok) != 0) {
-                const float p = q.template score<SG>(f, O, ok ? jr : 0, c, h, true);
-                if (h == 0 && ok) {                                // element 0 of lane r: row 0, column r
-                    lacc += dt * (rtk_clog(p) - rtk_clog(1.0f - p));
-                    dz = (p == 1.0f || p == 0.0f) ? 0.f : -dt;
-                }
-            }
-            if (off && h == 0 && i < i1) {
-                const int64_t at = (int64_t)off[d] + (i - i0);
-                if (at < max_pos) {
-                    ent[at] = ok ? (int32_t)jr : N;
-                    owner[at] = d;
-                    dzf[at] = dz;
-                }
-            }
-            if (dvpos) {
-                for (int rr = 0; rr < 32; ++rr) {
-                    const float g = __shfl(dz, rr);
-                    const int j = __shfl((int)(ok ? jr : 0), rr);
-                    if (g != 0.f) {                                // (uniform)
-                        const float *oj = O + (int64_t)j * c;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (lane + 64 * k < c) dva[k] = fmaf(g, oj[lane + 64 * k], dva[k]);
-                    }
-                }
-            }
-        }
-    }
-    if (rows_pos) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) lacc += __shfl_xor(lacc, o);
-        if (lane == 0) rows_pos[(int64_t)d * BS_POS_Y + wave] = -(double)lacc;
-    }
-    if (dvpos) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) part[wave][lane + 64 * k] = dva[k];
-        __syncthreads();
-        const int col = threadIdx.x;
-        if (col < c) dvpos[(int64_t)d * c + col] = ((part[0][col] + part[1][col]) + part[2][col]) + part[3][col];
-    }
-}
-
-// vs = scale * v (the small operand of gO carries g / (B N))
-__global__ __launch_bounds__(256) void scale_v_kernel(const float *__restrict__ v, int64_t n, const float *__restrict__ scale,
-                                                      float *__restrict__ vs) {
-    const float s = scale[0];
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) vs[i] = v[i] * s;
-}
-
-// the transposed images of vs, one per query tile, scaled by the power of two of its largest magnitude
-__global__ __launch_bounds__(256) void pack_v_kernel(const float *__restrict__ vs, int B, int c, int nct,
-                                                     const float *__restrict__ v_bound, _Float16 *__restrict__ vp) {
-    const int mt = blockIdx.x, cp = 32 * nct;
-    const float up = ldexpf(1.0f, rtk_pack_shift(v_bound[0]));
-    _Float16 *img = vp + (int64_t)mt * nct * 2048;
-    for (int i = threadIdx.x; i < 32 * cp; i += 256) {
-        const int j = i / cp, col = i - j * cp, d = mt * 32 + j;
-        const float y = (d < B && col < c) ? vs[(int64_t)d * c + col] * up : 0.f;
-        const _Float16 hi = (_Float16)y;
-        const int ix = timg_index(j, col);
-        img[ix] = hi;
-        img[nct * 1024 + ix] = (_Float16)(y - (float)hi);
-    }
-}
-
-template <int KS>
-struct GoLds {
-    static constexpr int TILE = (int)tile_bytes<float, KS>();      // the packed query tile (header + two planes)
-    static constexpr int EXTRA = timg_bytes(KS);                   // ... and the tile's image of s v behind it
-    static constexpr int TOTAL = 2 * (TILE + EXTRA);
-};
-
-// What go_kernel does with the sweep: the tile of x is the A operand of X^T V against the image of s v that travels
-// with the query tile; a wave's 32 rows of gO are accumulated over the query tiles and stored once per entity tile.
-template <int KS, int SG>
-struct GoSweep {
-    static constexpr int NCT = nct_of(KS);
-    static constexpr int EXTRA = GoLds<KS>::EXTRA;
-    static constexpr int NLV = EXTRA / 16 / (64 * BS_WAVES);        // 16-byte pieces of the image per thread: NCT
-    static_assert(EXTRA % (16 * 64 * BS_WAVES) == 0, "the image of s v is staged without a bound: whole pieces per thread");
-    const unsigned char *__restrict__ vp;
-    int B, N, c;
-    float t0, un;
-    float *__restrict__ gO;
-    u32x4 vstg[NLV];
-    f32x16 gacc[NCT];
-
-    __device__ __forceinline__ void load_extra(SweepLane ln, int mt) {
-        const u32x4 *sv = reinterpret_cast<const u32x4 *>(vp + (int64_t)mt * EXTRA);
-#pragma unroll
-        for (int i = 0; i < NLV; ++i) vstg[i] = sv[i * 64 * BS_WAVES + ln.t];
-    }
-    __device__ __forceinline__ void store_extra(SweepLane ln, int extra) const {
-        u32x4 *dst = reinterpret_cast<u32x4 *>(sweep_lds + extra);
-#pragma unroll
-        for (int i = 0; i < NLV; ++i) dst[i * 64 * BS_WAVES + ln.t] = vstg[i];
-    }
-    __device__ __forceinline__ void begin_tile() {
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) gacc[ct] = zero16();
-    }
-    // element e: query row acc_row(e, h) of the tile, entity r of the wave
-    __device__ __forceinline__ void score(SweepLane ln, const Frag<float, KS> &f, const f32x16 &acc,
-                                          const unsigned char *buf, int, int, bool, int mt) {
-        float x[16];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int rw = acc_row(4 * g, ln.h);
-            const f32x4 sr4 = *reinterpret_cast<const f32x4 *>(buf + rw * 4);
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const float p = f.template prob<SG>(acc[4 * g + q], sr4[q]);
-                x[4 * g + q] = x_of(p, t0, mt * 32 + rw + q < B);
-            }
-        }
-        f16x8 xh[2], xl[2];
-        split_x(x, xh, xl);
-        tile_product<NCT>(xh, xl, reinterpret_cast<const f16x8 *>(buf + GoLds<KS>::TILE), ln.lane, gacc);
-    }
-    __device__ __forceinline__ void publish(SweepLane, int, int, int, int, int, bool) const {}
-    // element e of gacc[ct]: entity row acc_row(e, h) of the wave, column 32 ct + r; on top of the positives' share
-    // that the ordered scatter wrote
-    __device__ __forceinline__ void end_tile(SweepLane ln, int tile) const {
-        const int j0 = tile * SW_TILE + ln.wave * 32;                // the wave's first row
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) {
-            const int col = ct * 32 + ln.r;
-#pragma unroll
-            for (int e = 0; e < 16; ++e) {
-                const int j = j0 + acc_row(e, ln.h);
-                if (j < N && col < c) {
-                    float *dst = gO + (int64_t)j * c + col;
-                    *dst = gacc[ct][e] * un + *dst;
-                }
-            }
-        }
+// the positives' link: the correction -(1 - eps) (ln p - ln(1 - p)) and dz = -(1 - eps), 0 where p is saturated
+struct BcePos {
+    static __device__ __forceinline__ float coef(float dt, int64_t) { return dt; }
+    template <int SG, int KS>
+    static __device__ __forceinline__ void term(const Frag<float, KS> &f, float acc, float srow, float dt, float &lacc,
+                                                float &dz) {
+        const float p = f.template prob<SG>(acc, srow);
+        lacc += dt * (rtk_clog(p) - rtk_clog(1.0f - p));
+        dz = (p == 1.0f || p == 0.0f) ? 0.f : -dt;
     }
 };
 
-// Sweep 2.  Workgroup w: entity tiles (128 rows) w, w + grid, ...; every query tile.
-template <int KS, int SG>
-__global__ __launch_bounds__(64 * BS_WAVES, 1) void go_kernel(const unsigned char *__restrict__ qp,
-                                                              const unsigned char *__restrict__ vp, int B,
-                                                              const float *__restrict__ O, int N, int c, float t0,
-                                                              const float *__restrict__ v_bound, float *__restrict__ gO) {
-    GoSweep<KS, SG> pol{vp, B, N, c, t0, ldexpf(1.0f, -14 - rtk_pack_shift(v_bound[0])), gO};
-    sweep<float, KS, SG>(pol, qp, B, O, N, c, true, (int)gridDim.x, 1);
-}
+// sweep 2's link: nothing travels with the query tile
+struct BceGo {
+    static constexpr int QB = 0;
+    float t0;
+    __device__ __forceinline__ void rows4(const unsigned char *, int) {}
+    template <int SG, int KS>
+    __device__ __forceinline__ float x(const Frag<float, KS> &f, float acc, float srow, int, bool valid) const {
+        return x_of(f.template prob<SG>(acc, srow), t0, valid);
+    }
+};
 
 // ---- host side -------------------------------------------------------------------------------------------------
-
-int splits_of(int64_t batch) {
-    const int64_t n_qg = rtk_cdiv(rtk_cdiv(batch, 32), BS_WAVES);
-    const int64_t s = RTK_N_CU / (n_qg > 0 ? n_qg : 1);
-    return (int)(s < 1 ? 1 : s);
-}
 
 struct StreamWs {
     size_t bounds, part_loss, rows_pos, slab, dvpos, vs, vp, off, ent, owner, dzf, sort, total;
@@ -566,7 +184,7 @@ int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, in
         const int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
         if (rc != RTK_OK) return rc;
     }
-    hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot, ptr,
+    hipLaunchKernelGGL((pos_kernel<KS, SG, BcePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot, ptr,
                        obj, rows_pos, dv ? dvpos : nullptr, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
                        (int32_t *)nullptr, (float *)nullptr);
     constexpr int bytes = RowsLds<KS>::TOTAL;
@@ -587,36 +205,9 @@ template <int KS, int SG>
 int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, int n_ent,
                   const int64_t *slot, const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps,
                   const float *scale, float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
-    const float t0 = eps / (float)n_ent, dt = 1.0f - eps;
-    constexpr int NCT = nct_of(KS);
-    const int n_mt = (int)rtk_cdiv(B, 32);
-    uint32_t *err = reinterpret_cast<uint32_t *>(ws);
-    float *bounds = reinterpret_cast<float *>(ws + L.bounds), *vs = reinterpret_cast<float *>(ws + L.vs);
-    int32_t *off = reinterpret_cast<int32_t *>(ws + L.off), *ent = reinterpret_cast<int32_t *>(ws + L.ent);
-    int32_t *owner = reinterpret_cast<int32_t *>(ws + L.owner);
-    float *dzf = reinterpret_cast<float *>(ws + L.dzf);
-    const int64_t nv = (int64_t)B * c;
-    hipLaunchKernelGGL(scale_v_kernel, dim3((unsigned)(rtk_cdiv(nv, 256) < 1024 ? rtk_cdiv(nv, 256) : 1024)), dim3(256), 0, st,
-                       v, nv, scale, vs);
-    int rc = rtk_absmax_f32(vs, B, c, c, bounds + 1, (void *)st);
-    if (rc != RTK_OK) return rc;
-    hipLaunchKernelGGL(pack_v_kernel, dim3((unsigned)n_mt), dim3(256), 0, st, vs, B, c, NCT, bounds + 1,
-                       reinterpret_cast<_Float16 *>(ws + L.vp));
-    // the positives' share: flat lists, then the ordered scatter (which zeroes gO first)
-    if (max_pos > 0) {
-        hipLaunchKernelGGL(pos_fill_kernel, dim3((unsigned)(rtk_cdiv(max_pos, 256) < 1024 ? rtk_cdiv(max_pos, 256) : 1024)),
-                           dim3(256), 0, st, max_pos, (int32_t)N, ent, owner, dzf);
-        hipLaunchKernelGGL(pos_offsets_kernel, dim3(1), dim3(256), 0, st, B, slot, ptr, max_pos, off, err);
-        hipLaunchKernelGGL((pos_kernel<KS, SG>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot,
-                           ptr, obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
-    }
-    rc = rtk_cand_flat_scatter(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
-    if (rc != RTK_OK) return rc;
-    // one workgroup per CU: whole entity tiles per slot, no query ranges
-    const int n_slots = grid_of(B, N, RTK_N_CU).n_slots;
-    return launch_lds<&go_kernel<KS, SG>, GoLds<KS>::TOTAL>(dim3((unsigned)n_slots), dim3(64 * BS_WAVES), st, fn, qp,
-                                                            (const unsigned char *)(ws + L.vp), B, O, N, c, t0,
-                                                            (const float *)(bounds + 1), gO);
+    const GoWs G{L.bounds, L.vs, L.vp, L.off, L.ent, L.owner, L.dzf, L.sort};
+    return launch_go<KS, SG, BcePos>(qp, v, B, c, O, N, col0, slot, ptr, obj, max_pos, 1.0f - eps, scale,
+                                     BceGo{eps / (float)n_ent}, (const unsigned char *)nullptr, gO, ws, G, st, fn);
 }
 
 // The two sweeps on rows [col0, col0 + n_local) of the (n_ent x c) matrix; the whole matrix is the block (0, n_ent).

@@ -1,0 +1,355 @@
+// The 1-vs-all softmax cross-entropy training loss and its gradients without the (B, N) logit matrix: the sweeps of
+// rtk_bce_stream.hip (rtk_stream_kernel.h) with another link function.  With P_d the CSR list of query d, n_d its
+// length, t0 = eps / N and w_d = (1 - eps) [n_d > 0] + eps (the mass of the row's targets),
+//
+//     loss_rows[d] = w_d lse_d - t0 sum_j z[d, j] - (1 - eps) / n_d sum_{t in P_d} z[d, t],
+//     x[d, j]      = w_d exp(z[d, j] - lse_d) - t0      (every valid column: there is no saturation rule),
+//
+// and the positives are the sparse correction -(1 - eps) / n_d per CSR entry.  z is Frag<float, KS>'s accumulated value
+// times the row and column factors, acc * (srow * 2^-sh): the logit of the score kernels, without the logistic.
+//
+//   ce_fwd_kernel    the forward, sweep 1 without the second tile product: each lane keeps an online (maximum, sum of
+//                    exp) and the sum of z of its query over its 16 entities per tile; partials per split.
+//   ce_finish_kernel merges the splits' partials in split order in float64, adds the positives' term (pos_kernel with
+//                    the CE link) and gives loss_rows and lse.
+//   ce_dv_kernel     backward sweep 1 with the second tile product: dv[d, :] = sum_j x[d, j] O[j, :].
+//   go_kernel        backward sweep 2 with the CE link: the tile's 32 values of lse and w travel with the query tile.
+//
+// Every sum has a fixed order; no float atomics; nothing grows with B x N.
+#include "rtk_stream_kernel.h"
+
+namespace {
+
+constexpr int CE_SG = 1;                        // plain column factors 2^-sh (no logistic is taken)
+constexpr float CE_L2E = 1.4426950408889634f;
+constexpr float CE_NONE = -3.0e38f;             // the running maximum before the first valid column
+
+__device__ __forceinline__ float ce_exp(float a) { return __builtin_amdgcn_exp2f(a * CE_L2E); }
+
+// the mass of query d's targets and the weight of one of its positives
+__device__ __forceinline__ int64_t ce_list_len(int d, const int64_t *__restrict__ pair_slot,
+                                               const int64_t *__restrict__ pair_ptr) {
+    const int64_t s = pair_slot[d];
+    const int64_t n = s >= 0 ? pair_ptr[s + 1] - pair_ptr[s] : 0;
+    return n > 0 ? n : 0;
+}
+
+// the forward's link: online log-sum-exp and the sum of z per query
+template <int KS>
+struct CeFwdRows {
+    float *__restrict__ part_max;
+    double *__restrict__ part_sum, *__restrict__ part_z;
+    float M;
+    double S, SZ;
+    __device__ __forceinline__ void begin(int, bool) {
+        M = CE_NONE;
+        S = SZ = 0.0;
+    }
+    __device__ __forceinline__ void tile(const f32x16 &acc, float srow, const unsigned char *kc, int tile, int h, int N,
+                                         float (&)[16]) {
+        float z[16];
+        float m = M, zs = 0.f;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 kc4 = *reinterpret_cast<const f32x4 *>(kc + (8 * g + 4 * h) * 4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * g + q;
+                const bool valid = tile * 32 + 8 * g + 4 * h + q < N;
+                z[e] = valid ? acc[e] * (srow * kc4[q]) : CE_NONE;      // a column past N: -inf for the lse, 0 for the sum
+                zs += valid ? z[e] : 0.f;
+                m = fmaxf(m, z[e]);
+            }
+        }
+        float ts = 0.f;
+#pragma unroll
+        for (int e = 0; e < 16; ++e) ts += z[e] > CE_NONE ? ce_exp(z[e] - m) : 0.f;
+        S = S * (double)ce_exp(M - m) + (double)ts;
+        M = m;
+        SZ += (double)zs;
+    }
+    __device__ __forceinline__ void finish(int sp, int d, int h, int B) {
+        const float Mo = __shfl_xor(M, 32);
+        const double So = __shfl_xor(S, 32), SZo = __shfl_xor(SZ, 32);
+        if (h == 0 && d < B) {                                     // the lane pair's halves, h = 0 first
+            const float m = fmaxf(M, Mo);
+            const int64_t at = (int64_t)sp * B + d;
+            part_max[at] = m;
+            part_sum[at] = S * (double)ce_exp(M - m) + So * (double)ce_exp(Mo - m);
+            part_z[at] = SZ + SZo;
+        }
+    }
+};
+
+// backward sweep 1's link: x from the query's lse and w (one query per lane)
+template <int KS>
+struct CeDvRows {
+    const float *__restrict__ lw;               // per query tile: 32 lse, 32 w
+    float t0;
+    float lse, w;
+    __device__ __forceinline__ void begin(int d, bool on) {
+        lse = on ? lw[(d >> 5) * 64 + (d & 31)] : 0.f;
+        w = on ? lw[(d >> 5) * 64 + 32 + (d & 31)] : 0.f;
+    }
+    __device__ __forceinline__ void tile(const f32x16 &acc, float srow, const unsigned char *kc, int tile, int h, int N,
+                                         float (&x)[16]) {
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 kc4 = *reinterpret_cast<const f32x4 *>(kc + (8 * g + 4 * h) * 4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = 4 * g + q;
+                const bool valid = tile * 32 + 8 * g + 4 * h + q < N;
+                x[e] = valid ? w * ce_exp(acc[e] * (srow * kc4[q]) - lse) - t0 : 0.f;
+            }
+        }
+    }
+    __device__ __forceinline__ void finish(int, int, int, int) {}
+};
+
+template <int KS>
+__global__ __launch_bounds__(64 * BS_WAVES, 1) void ce_fwd_kernel(const unsigned char *__restrict__ qp, int B,
+                                                                  const float *__restrict__ O, int N, int c, int n_splits,
+                                                                  float *__restrict__ part_max,
+                                                                  double *__restrict__ part_sum,
+                                                                  double *__restrict__ part_z) {
+    CeFwdRows<KS> pol{part_max, part_sum, part_z, CE_NONE, 0.0, 0.0};
+    rows_sweep<KS, CE_SG, false>(pol, qp, B, O, N, c, (const float *)nullptr, n_splits, (float *)nullptr);
+}
+
+template <int KS>
+__global__ __launch_bounds__(64 * BS_WAVES, 1) void ce_dv_kernel(const unsigned char *__restrict__ qp, int B,
+                                                                 const float *__restrict__ O, int N, int c, float t0,
+                                                                 const float *__restrict__ lw,
+                                                                 const float *__restrict__ o_bound, int n_splits,
+                                                                 float *__restrict__ slab) {
+    CeDvRows<KS> pol{lw, t0, 0.f, 0.f};
+    rows_sweep<KS, CE_SG, true>(pol, qp, B, O, N, c, o_bound, n_splits, slab);
+}
+
+// The splits' partials in split order, in float64: lse_d = M + ln sum_k S_k exp(M_k - M) (a split without a tile has
+// S_k = 0), then loss_rows[d] = w_d lse_d - t0 sum_k SZ_k + the positives' term.  One thread per query.
+__global__ __launch_bounds__(256) void ce_finish_kernel(int B, int n_splits, double t0, double eps,
+                                                        const float *__restrict__ part_max,
+                                                        const double *__restrict__ part_sum,
+                                                        const double *__restrict__ part_z,
+                                                        const double *__restrict__ rows_pos,
+                                                        const int64_t *__restrict__ pair_slot,
+                                                        const int64_t *__restrict__ pair_ptr,
+                                                        double *__restrict__ loss_rows, float *__restrict__ lse_out) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= B) return;
+    float m = CE_NONE;
+    for (int k = 0; k < n_splits; ++k) m = fmaxf(m, part_max[(int64_t)k * B + d]);
+    double s = 0.0, sz = 0.0;
+    for (int k = 0; k < n_splits; ++k) {
+        const int64_t at = (int64_t)k * B + d;
+        const double sk = part_sum[at];
+        if (sk > 0.0) s += sk * exp((double)part_max[at] - (double)m);
+        sz += part_z[at];
+    }
+    const double lse = (double)m + log(s);
+    double pcor = 0.0;
+#pragma unroll
+    for (int u = 0; u < BS_POS_Y; ++u) pcor += rows_pos[(int64_t)d * BS_POS_Y + u];
+    const double w = (ce_list_len(d, pair_slot, pair_ptr) > 0 ? 1.0 - eps : 0.0) + eps;
+    loss_rows[d] = w * lse - t0 * sz + pcor;
+    lse_out[d] = (float)lse;
+}
+
+// lw of query tile mt: lse of its 32 queries, then their w; queries past B carry zeros
+__global__ __launch_bounds__(256) void ce_lw_kernel(int B, int n_pad, float eps, const float *__restrict__ lse,
+                                                    const int64_t *__restrict__ pair_slot,
+                                                    const int64_t *__restrict__ pair_ptr, float *__restrict__ lw) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= n_pad) return;
+    const bool in = d < B;
+    lw[(d >> 5) * 64 + (d & 31)] = in ? lse[d] : 0.f;
+    lw[(d >> 5) * 64 + 32 + (d & 31)] = in ? (ce_list_len(d, pair_slot, pair_ptr) > 0 ? 1.0f - eps : 0.f) + eps : 0.f;
+}
+
+// dv[d, :] = the splits' slabs + the positives' share.  One workgroup per query.
+__global__ __launch_bounds__(256) void ce_dv_finish_kernel(int B, int c, int cp, int n_splits, const float *__restrict__ slab,
+                                                           const float *__restrict__ dvpos,
+                                                           const float *__restrict__ o_bound, float *__restrict__ dv) {
+    finish_dv_row(blockIdx.x, threadIdx.x, B, c, cp, n_splits, slab, dvpos, o_bound, dv);
+}
+
+// the positives' link: every entry of a list of n carries (1 - eps) / n of the target mass; the loss is linear in z
+struct CePos {
+    static __device__ __forceinline__ float coef(float dt, int64_t n) { return n > 0 ? dt / (float)n : 0.f; }
+    template <int SG, int KS>
+    static __device__ __forceinline__ void term(const Frag<float, KS> &f, float acc, float srow, float cf, float &lacc,
+                                                float &dz) {
+        lacc += cf * (acc * (srow * f.kcol));
+        dz = -cf;
+    }
+};
+
+// sweep 2's link: the tile's 32 values of lse and of w travel behind the image of s v
+struct CeGo {
+    static constexpr int QB = 256;
+    float t0;
+    f32x4 l4, w4;
+    __device__ __forceinline__ void rows4(const unsigned char *q4, int rw) {
+        l4 = *reinterpret_cast<const f32x4 *>(q4 + rw * 4);
+        w4 = *reinterpret_cast<const f32x4 *>(q4 + 128 + rw * 4);
+    }
+    template <int SG, int KS>
+    __device__ __forceinline__ float x(const Frag<float, KS> &f, float acc, float srow, int q, bool valid) const {
+        return valid ? w4[q] * ce_exp(acc * (srow * f.kcol) - l4[q]) - t0 : 0.f;
+    }
+};
+
+// ---- host side -------------------------------------------------------------------------------------------------
+
+struct CeWs {
+    size_t bounds, part_max, part_sum, part_z, rows_pos, slab, dvpos, vs, vp, lw, off, ent, owner, dzf, sort, total;
+};
+CeWs layout_of(int64_t batch, int c, int64_t max_pos) {
+    CeWs L;
+    const int ks = (c + 15) / 16, nct = nct_of(ks);
+    const size_t B = (size_t)batch, S = (size_t)splits_of(batch), n_mt = (size_t)rtk_cdiv(batch, 32);
+    const size_t M = (size_t)(max_pos > 0 ? max_pos : 0);
+    size_t at = 256;                                          // [0, 256): the error word's header
+    auto take = [&](size_t bytes) {
+        const size_t p = at;
+        at += rtk_align_up(bytes, 256);
+        return p;
+    };
+    L.bounds = take(256);                                     // max |O|, max |s v|
+    L.part_max = take(S * B * 4);
+    L.part_sum = take(S * B * 8);
+    L.part_z = take(S * B * 8);
+    L.rows_pos = take(B * BS_POS_Y * 8);
+    L.slab = take(S * B * 32 * nct * 4);
+    L.dvpos = take(B * (size_t)c * 4);
+    L.vs = take(B * (size_t)c * 4);
+    L.vp = take(n_mt * (size_t)nct * 4096);
+    L.lw = take(n_mt * 256);
+    L.off = take((B + 1) * 4);
+    L.ent = take(M * 4);
+    L.owner = take(M * 4);
+    L.dzf = take(M * 4);
+    L.sort = take(rtk_cand_flat_workspace_bytes((int64_t)M));
+    L.total = at;
+    return L;
+}
+
+int check_ce(const char *fn, bool operands, int64_t batch, int c, const float *O, int64_t n_ent, int64_t max_pos, float eps,
+             const void *workspace, size_t ws_bytes) {
+    const auto own = [&]() -> int {
+        RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
+        RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
+        RTK_REQUIRE(max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
+        return RTK_OK;
+    };
+    // (the entries take logits and have no flags: what = nullptr)
+    return check_block(fn, operands, batch, c, O, n_ent, 0, n_ent, own, (1ll << 31) - 256, 0u, (const char *)nullptr, workspace,
+                       ws_bytes, [&] { return layout_of(batch, c, max_pos).total; });
+}
+
+template <int KS>
+int launch_fwd(const unsigned char *qp, int B, int c, const float *O, int N, const int64_t *slot, const int64_t *ptr,
+               const int64_t *obj, float eps, double *loss_rows, float *lse, unsigned char *ws, const CeWs &L,
+               hipStream_t st) {
+    const int splits = splits_of(B), n_qg = (int)rtk_cdiv(rtk_cdiv(B, 32), BS_WAVES);
+    float *part_max = reinterpret_cast<float *>(ws + L.part_max);
+    double *part_sum = reinterpret_cast<double *>(ws + L.part_sum), *part_z = reinterpret_cast<double *>(ws + L.part_z);
+    double *rows_pos = reinterpret_cast<double *>(ws + L.rows_pos);
+    hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, 0, c,
+                       1.0f - eps, slot, ptr, obj, rows_pos, (float *)nullptr, (const int32_t *)nullptr, (int64_t)0,
+                       (int32_t *)nullptr, (int32_t *)nullptr, (float *)nullptr);
+    constexpr int bytes = RowsLds<KS>::TOTAL;
+    static_assert(bytes <= 64 * 1024, "ce_fwd_kernel: one 32-row tile in two layouts fits the default LDS limit");
+    RTK_LAUNCH_SCORE((ce_fwd_kernel<KS>), dim3((unsigned)(n_qg * splits)), dim3(64 * BS_WAVES), bytes, st, qp, B, O, N, c,
+                     splits, part_max, part_sum, part_z);
+    hipLaunchKernelGGL(ce_finish_kernel, dim3((unsigned)rtk_cdiv(B, 256)), dim3(256), 0, st, B, splits,
+                       (double)eps / (double)N, (double)eps, (const float *)part_max, (const double *)part_sum,
+                       (const double *)part_z, (const double *)rows_pos, slot, ptr, loss_rows, lse);
+    return RTK_OK;
+}
+
+template <int KS>
+int launch_grad(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, const int64_t *slot,
+                const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps, const float *lse, const float *scale,
+                float *dv, float *gO, unsigned char *ws, const CeWs &L, hipStream_t st, const char *fn) {
+    const float t0 = eps / (float)N, dt = 1.0f - eps;
+    constexpr int NCT = nct_of(KS);
+    const int n_mt = (int)rtk_cdiv(B, 32), splits = splits_of(B), n_qg = (int)rtk_cdiv(n_mt, BS_WAVES);
+    float *bounds = reinterpret_cast<float *>(ws + L.bounds);
+    float *slab = reinterpret_cast<float *>(ws + L.slab), *dvpos = reinterpret_cast<float *>(ws + L.dvpos);
+    float *lw = reinterpret_cast<float *>(ws + L.lw);
+    hipLaunchKernelGGL(ce_lw_kernel, dim3((unsigned)rtk_cdiv(32 * n_mt, 256)), dim3(256), 0, st, B, 32 * n_mt, eps, lse, slot,
+                       ptr, lw);
+    if (dv) {                                                     // sweep 1 with the second tile product
+        int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
+        if (rc != RTK_OK) return rc;
+        hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, 0, c, dt,
+                           slot, ptr, obj, (double *)nullptr, dvpos, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
+                           (int32_t *)nullptr, (float *)nullptr);
+        constexpr int bytes = RowsLds<KS>::TOTAL;
+        RTK_LAUNCH_SCORE((ce_dv_kernel<KS>), dim3((unsigned)(n_qg * splits)), dim3(64 * BS_WAVES), bytes, st, qp, B, O, N, c, t0,
+                         (const float *)lw, (const float *)bounds, splits, slab);
+        hipLaunchKernelGGL(ce_dv_finish_kernel, dim3((unsigned)B), dim3(256), 0, st, B, c, 32 * NCT, splits,
+                           (const float *)slab, (const float *)dvpos, (const float *)bounds, dv);
+    }
+    if (!gO) return RTK_OK;
+    const GoWs G{L.bounds, L.vs, L.vp, L.off, L.ent, L.owner, L.dzf, L.sort};
+    return launch_go<KS, CE_SG, CePos>(qp, v, B, c, O, N, 0, slot, ptr, obj, max_pos, dt, scale, CeGo{t0},
+                                       (const unsigned char *)lw, gO, ws, G, st, fn);
+}
+
+template <typename F>
+int dispatch_ce(const char *fn, int c, F f) {
+    const int rc = rtk_dispatch_ksteps<SW_MAX_KS_F32>((c + 15) / 16, fn, f);
+    return rc != RTK_OK ? rc : rtk_check_launch(fn);
+}
+
+}  // namespace
+
+extern "C" size_t rtk_ce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
+    if (batch < 0 || n_ent < 1 || c < 1 || c > 16 * BS_MAX_KS || max_pos < 0 || max_pos >= (1ll << 31) - 1) return 0;
+    return layout_of(batch, c, max_pos).total;
+}
+
+extern "C" int rtk_ce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
+                                      const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                                      float label_smoothing, double *loss_rows_out, float *lse_out, void *workspace,
+                                      size_t ws_bytes, void *stream) {
+    const char *fn = "rtk_ce_stream_rows_f32";
+    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && loss_rows_out && lse_out, batch, c, O, n_ent, 0,
+                      label_smoothing, workspace, ws_bytes);
+    if (rc != RTK_OK || batch == 0) return rc;
+    const CeWs L = layout_of(batch, c, 0);
+    return dispatch_ce(fn, c, [&](auto K) {
+        return launch_fwd<K.value>((const unsigned char *)q_packed, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj,
+                                   label_smoothing, loss_rows_out, lse_out, (unsigned char *)workspace, L, (hipStream_t)stream);
+    });
+}
+
+extern "C" int rtk_ce_stream_grad_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O,
+                                      int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                      const int64_t *pair_obj, int64_t max_pos, float label_smoothing, const float *lse,
+                                      const float *scale, float *dv_out, float *gO_out, void *workspace, size_t ws_bytes,
+                                      void *stream) {
+    const char *fn = "rtk_ce_stream_grad_f32";
+    RTK_REQUIRE(!gO_out || (v && scale), RTK_ERR_BAD_ARG, "%s: null operand", fn);
+    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && lse && (dv_out || gO_out), batch, c, O, n_ent,
+                      max_pos, label_smoothing, workspace, ws_bytes);
+    if (rc != RTK_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (batch == 0) {                                         // no term touches any row
+        if (gO_out && hipMemsetAsync(gO_out, 0, (size_t)n_ent * c * 4, st) != hipSuccess) {
+            rtk_set_error("%s: memset failed", fn);
+            return RTK_ERR_LAUNCH;
+        }
+        return RTK_OK;
+    }
+    const CeWs L = layout_of(batch, c, max_pos);
+    return dispatch_ce(fn, c, [&](auto K) {
+        return launch_grad<K.value>((const unsigned char *)q_packed, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr,
+                                    pair_obj, max_pos, label_smoothing, lse, scale, dv_out, gO_out, (unsigned char *)workspace,
+                                    L, st, fn);
+    });
+}

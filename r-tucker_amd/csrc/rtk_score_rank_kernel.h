@@ -359,8 +359,9 @@ bool vec_rows(const T *O, int c) { return sizeof(T) == 4 || (c % 8 == 0 && (rein
 // The checks every entry point on a block [col0, col0 + n_local) of O shares.  `operands`: whether the call's own
 // pointers are all there; `own()`: the refusals of the call's own arguments (k, max_pos, ...), tested where the callers
 // had them, after the bad arguments and before the unsupported ones, so that a call with several faults keeps its
-// return code; `n_ent_limit`: the call's bound on n_ent; `what`: what the call takes on probabilities; `need()`: the
-// workspace bytes of the call (asked once the shape is known to be sound).
+// return code; `n_ent_limit`: the call's bound on n_ent; `what`: what the call takes on probabilities (nullptr: an entry
+// on logits, which has no flags -- `flags` is not looked at); `need()`: the workspace bytes of the call (asked once the
+// shape is known to be sound).
 template <typename T, typename FO, typename F>
 int check_block(const char *fn, bool operands, int64_t batch, int c, const T *O, int64_t n_local, int64_t col0, int64_t n_ent,
                 FO own, int64_t n_ent_limit, unsigned flags, const char *what, const void *workspace, size_t ws_bytes, F need) {
@@ -374,10 +375,12 @@ int check_block(const char *fn, bool operands, int64_t batch, int c, const T *O,
     const int rc = own();
     if (rc != RTK_OK) return rc;
     RTK_REQUIRE(batch < (1ll << 31) - 32 && n_ent < n_ent_limit, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
-    RTK_REQUIRE(flags & RTK_SCORE_SIGMOID, RTK_ERR_UNSUPPORTED,
-                "%s: %s taken on probabilities: flags need RTK_SCORE_SIGMOID (raw logits are not covered)", fn, what);
-    RTK_REQUIRE((flags & ~(RTK_SCORE_SIGMOID | RTK_SCORE_SIGMOID_FAST)) == 0, RTK_ERR_BAD_ARG, "%s: unknown flags 0x%x",
-                fn, flags);
+    if (what) {
+        RTK_REQUIRE(flags & RTK_SCORE_SIGMOID, RTK_ERR_UNSUPPORTED,
+                    "%s: %s taken on probabilities: flags need RTK_SCORE_SIGMOID (raw logits are not covered)", fn, what);
+        RTK_REQUIRE((flags & ~(RTK_SCORE_SIGMOID | RTK_SCORE_SIGMOID_FAST)) == 0, RTK_ERR_BAD_ARG, "%s: unknown flags 0x%x",
+                    fn, flags);
+    }
     if (sizeof(T) == 4) {
         RTK_REQUIRE(c <= 16 * SW_MAX_KS_F32, RTK_ERR_UNSUPPORTED, "%s: c = %d above %d (the ws kernel's range)", fn, c,
                     16 * SW_MAX_KS_F32);

@@ -15,6 +15,8 @@ The shuffle uses ``torch.randperm`` on the device with ``drop_last`` semantics (
 """
 from __future__ import annotations
 
+import functools
+
 import torch
 from torch import nn
 
@@ -69,12 +71,19 @@ class RegularisedLoss:
         return self.data_term(T) + self.coeff * T.norm() ** 2
 
 
+LOSSES = ("bce", "ce")          # TrainConfig.loss
+
+
 def batch_loss_fn(model, subject_idx, relation_idx, flt, item_ids, label_smoothing, regularization_coeff,
-                  matrix_free=False):
+                  matrix_free=False, loss="bce"):
     """``loss_fn`` of ``train.py:79`` for one batch, as a function of the container ``T``.
     ``regularization_coeff``: a float or a 0-dim device tensor (the captured step keeps it in device memory).
     ``matrix_free``: ``ops.bce_loss_1vN``'s form without the (B, N) matrix (object rank <= 208: not the Riemannian
-    step's doubled-rank construct)."""
+    step's doubled-rank construct).  ``loss``: ``"bce"`` (the reference's) or ``"ce"``, the softmax cross-entropy
+    ``ops.ce_loss_1vN`` over the entities with the same smoothed targets normalised per row."""
+    if loss not in LOSSES:
+        raise ValueError(f"batch_loss_fn: unknown loss {loss!r} (one of {', '.join(LOSSES)})")
+    data_loss = ops.bce_loss_1vN if loss == "bce" else ops.ce_loss_1vN
     sym = _is_symmetric(model)
 
     def bce(T):
@@ -82,8 +91,8 @@ def batch_loss_fn(model, subject_idx, relation_idx, flt, item_ids, label_smoothi
             core, R, S, O = T.core, T.regular_factors[0], T.shared_factor, T.shared_factor
         else:
             core, (R, S, O) = T.core, T.factors
-        return ops.bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=label_smoothing,
-                                matrix_free=matrix_free)
+        return data_loss(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=label_smoothing,
+                         matrix_free=matrix_free)
 
     return RegularisedLoss(bce, regularization_coeff)
 
@@ -130,18 +139,21 @@ class EagerTrainStep:
 TRAIN_STEP_FACTORY = EagerTrainStep
 
 
-def _captured_step(model, optimizer, train_flt, batch_size, label_smoothing):
+def _captured_step(model, optimizer, train_flt, batch_size, label_smoothing, loss="bce"):
     """The per-batch step object, kept on the optimizer so that later epochs reuse it (and its device buffers)."""
-    key = (id(model), id(train_flt), int(batch_size), float(label_smoothing), TRAIN_STEP_FACTORY)
+    if loss not in LOSSES:
+        raise ValueError(f"train_cfg.loss: unknown loss {loss!r} (one of {', '.join(LOSSES)})")
+    key = (id(model), id(train_flt), int(batch_size), float(label_smoothing), TRAIN_STEP_FACTORY, loss)
     cur = getattr(optimizer, "_rtk_captured", None)
     if cur is None or cur[0] != key:
-        cur = (key, TRAIN_STEP_FACTORY(model, optimizer, train_flt, batch_size, label_smoothing, extract_tensor, batch_loss_fn))
+        loss_fn = batch_loss_fn if loss == "bce" else functools.partial(batch_loss_fn, loss=loss)
+        cur = (key, TRAIN_STEP_FACTORY(model, optimizer, train_flt, batch_size, label_smoothing, extract_tensor, loss_fn))
         optimizer._rtk_captured = cur
     return cur[1]
 
 
 def train_one_epoch(model, optimizer, train_flt: DeviceFilter, batch_size, label_smoothing, regularization_coeff=1e-4,
-                    max_batches=None, log=None):
+                    max_batches=None, log=None, loss="bce"):
     """``train.py:69-91``: one pass over the (s, r) pairs of the train split; returns the mean loss and mean
     Riemannian gradient norm over the batches.  The batch step (``fit`` + ``step``) runs eagerly (``EagerTrainStep``);
     loss and gradient norm are summed on the device (one synchronisation per epoch instead of the reference's two
@@ -153,7 +165,7 @@ def train_one_epoch(model, optimizer, train_flt: DeviceFilter, batch_size, label
     if max_batches is not None:
         n_batches = min(n_batches, max_batches)
     perm = torch.randperm(n, device=dev)
-    step = _captured_step(model, optimizer, train_flt, batch_size, label_smoothing)
+    step = _captured_step(model, optimizer, train_flt, batch_size, label_smoothing, loss)
     with ops.index_check("deferred"):                   # ids come from the dataset's own vocabulary: one check per epoch
         step.begin_epoch(regularization_coeff)
         for b in range(n_batches):
@@ -192,7 +204,8 @@ def train(model, optimizer, train_set, val_set, test_set, config, regulizer, sch
         with timer:
             train_loss, train_norm = train_one_epoch(model, optimizer, train_flt, tc.train_batch_size, tc.label_smoothig,
                                                      regularization_coeff=regularization_coeff,
-                                                     max_batches=max_batches_per_epoch)
+                                                     max_batches=max_batches_per_epoch,
+                                                     loss=getattr(tc, "loss", "bce"))
         epoch_time = timer.time
         val_metrics, val_loss = evaluate(model, val_set, tc.eval_batch_size, val_flt)
         with timer:

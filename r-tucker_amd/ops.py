@@ -767,6 +767,149 @@ def bce_loss_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx
                        label_smoothing, sigmoid_mode, max_pos, all_reduce)
 
 
+class _CeLoss1vN(torch.autograd.Function):
+    """mean softmax cross-entropy of the stored logits against the smoothed, per-row normalised targets given as a CSR
+    (``rtk_ce_rows_f32`` / ``rtk_ce_grad_f32``): the matrix form, any object rank."""
+
+    @staticmethod
+    def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, label_smoothing):
+        ctx.B = B = int(subject_idx.numel())
+        ctx.eps = float(label_smoothing)
+        if B == 0:
+            ctx.save_for_backward(core, R, S, O)
+            return torch.zeros((), dtype=torch.float32, device=core.device)
+        # the logits never leave this function pair: aligned rows for them
+        Z, v, op = _forward(core, R, S, O, subject_idx, relation_idx, False, False, want_v=True, padded=True)
+        lib = _lib.load()
+        dev = Z.device
+        N = Z.shape[1]
+        rows = torch.empty(B, dtype=torch.float64, device=dev)
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.rtk_ce_rows_f32(Z.data_ptr(), B, N, Z.stride(0) if B > 1 else N, pair_slot.data_ptr(),
+                                           pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, rows.data_ptr(), lse.data_ptr(),
+                                           _stream_ptr(dev)), "rtk_ce_rows_f32")
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, Z, lse, pair_slot, pair_ptr, pair_obj)
+        return (rows.sum() / B).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        needs = ctx.needs_input_grad
+        if ctx.B == 0:
+            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 6
+        core, R, S, O, h, r, v, Z, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
+        if getattr(ctx, "spent", False):
+            raise RuntimeError("ce_loss_1vN: backward called twice (the saved logits are overwritten by the first pass)")
+        ctx.spent = True
+        lib = _lib.load()
+        dev = Z.device
+        B, N = Z.shape
+        g = grad_loss.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+        with torch.cuda.device(dev):
+            # in place: Z <- (w softmax - y) * g / B = d loss / d logits  (the saved logits are spent)
+            _lib.check(lib.rtk_ce_grad_f32(Z.data_ptr(), B, N, Z.stride(0) if B > 1 else N, pair_slot.data_ptr(),
+                                           pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, lse.data_ptr(), g.data_ptr(),
+                                           1.0 / B, _stream_ptr(dev)), "rtk_ce_grad_f32")
+        # |dZ| = |w softmax - y| |g| / B <= |g| / B: the operand bound of the split-fp16 GEMMs, no pass over dZ
+        return _grads_from_dZ(core, R, S, O, h, r, v, Z, needs, core.dtype, dz_bound=g.abs() * (1.0 / B)) + (None,) * 6
+
+
+class _CeLossStream(torch.autograd.Function):
+    """``_CeLoss1vN`` without the logit matrix (``rtk_ce_stream_*``): one sweep (loss rows and lse) in the forward, two
+    (dv, gO) in the backward.  What is saved is of size B x c and B: the fp32 query vectors, their packed planes, lse."""
+
+    @staticmethod
+    def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, max_pos):
+        who = "ce_loss_1vN(matrix_free=True)"
+        core, R, S, O, h, r = _HipBlockLoss.operands(core, R, S, O, subject_idx, relation_idx, 0, O.shape[0], who)
+        ctx.B = B = h.numel()
+        ctx.eps, ctx.max_pos = float(eps), int(max_pos)
+        dev = core.device
+        if B == 0:
+            ctx.save_for_backward(core, R, S, O)
+            return torch.zeros((), dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        N, c = O.shape
+        v, qp = _HipBlockLoss.queries(core, R, S, h, r)
+        rows = torch.empty(B, dtype=torch.float64, device=dev)
+        lse = torch.empty(B, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_ce_stream_workspace_bytes", B, N, c, 0))
+            _lib.check(lib.rtk_ce_stream_rows_f32(qp.data_ptr(), B, c, O.data_ptr(), N, pair_slot.data_ptr(),
+                                                  pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, rows.data_ptr(),
+                                                  lse.data_ptr(), ws.data_ptr(), ws.numel(), sp), "rtk_ce_stream_rows_f32")
+        ctx.save_for_backward(core, R, S, O, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj)
+        return (rows.sum() / B).to(torch.float32)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        needs = ctx.needs_input_grad
+        if ctx.B == 0:
+            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 7
+        core, R, S, O, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
+        lib = _lib.load()
+        B, dev = ctx.B, core.device
+        N, c = O.shape
+        g = (grad_loss.to(device=dev, dtype=torch.float32).reshape(1) * (1.0 / B)).contiguous()
+        want_dv = any(needs[:3])
+        gcore = gR = gS = None
+        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
+        gO = torch.empty((N, c), dtype=torch.float32, device=dev) if needs[3] else None
+        if want_dv or needs[3]:
+            max_pos = ctx.max_pos if needs[3] else 0
+            with torch.cuda.device(dev):
+                sp = _stream_ptr(dev)
+                ws = _workspace(dev, sp, _size("rtk_ce_stream_workspace_bytes", B, N, c, max_pos))
+                _lib.check(lib.rtk_ce_stream_grad_f32(qp.data_ptr(), v.data_ptr(), B, c, O.data_ptr(), N, pair_slot.data_ptr(),
+                                                      pair_ptr.data_ptr(), pair_obj.data_ptr(), max_pos, ctx.eps,
+                                                      lse.data_ptr(), g.data_ptr(), dv.data_ptr() if want_dv else None,
+                                                      gO.data_ptr() if needs[3] else None, ws.data_ptr(), ws.numel(), sp),
+                           "rtk_ce_stream_grad_f32")
+                _strict_check(ws, sp)
+        if want_dv:
+            gcore, gR, gS = _stage1_backward(core, R, S, h, r, dv * g, needs)
+        return (gcore, gR, gS, gO) + (None,) * 7
+
+
+def ce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, matrix_free=False,
+                max_pos=None):
+    """The softmax cross-entropy 1-vs-all loss over the entities, the other standard training loss of link prediction
+    (what ``torch.nn.functional.cross_entropy(logits, y)`` with probability targets and mean reduction gives), WITHOUT
+    the dense target matrix: ``flt`` and ``item_ids`` as for ``bce_loss_1vN``.  With ``P_d`` the filter's list of item
+    d, ``n_d`` its length, N the entity count and eps the smoothing, the targets are
+    ``y[d, j] = (1 - eps) [j in P_d] / n_d + eps / N`` (the first term absent for an empty list), of row mass
+    ``w_d = (1 - eps) [n_d > 0] + eps``, and
+
+        loss = (1 / B) sum_d (w_d logsumexp(z_d) - sum_j y[d, j] z[d, j]),
+        d loss / d z[d, j] = (w_d softmax(z_d)_j - y[d, j]) / B.
+
+    The loss does not depend on the level of a row's logits.  Differentiable w.r.t. core and factors like
+    ``score_1vN``; a shared-factor model passes the same tensor as ``S`` and ``O``.
+
+    ``matrix_free=False``: on the stored logits of ``score_1vN(sigmoid=False)`` (``rtk_ce_rows_f32`` /
+    ``rtk_ce_grad_f32``), float32 operands at any object rank; one backward per forward.
+    ``matrix_free=True``: the same loss and gradients without the (B, N) matrix (``rtk_ce_stream_*``): what is kept
+    between forward and backward is B x c and B.  float32 operands with ``c <= 208``, ``c % 4 == 0`` (anything else
+    raises; there is no fallback).  Under ``no_grad`` only the forward sweep runs.  ``max_pos``: an upper bound on the
+    number of CSR entries of the batch's queries (default ``B * flt.max_list``, which always holds)."""
+    _require_gpu("core", core)
+    dev = core.device
+    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
+    if matrix_free:
+        if max_pos is None:
+            mx = getattr(flt, "max_list", None)
+            max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+        return _CeLossStream.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
+                                   float(label_smoothing), int(max_pos))
+    if max_pos is not None:
+        raise ValueError("max_pos belongs to matrix_free=True")
+    if core.dtype != torch.float32:
+        raise RuntimeError(f"ce_loss_1vN: float32 operands only, got {core.dtype}")
+    return _CeLoss1vN.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
+                            float(label_smoothing))
+
+
 def score_1vN(core, R, S, O, subject_idx, relation_idx, sigmoid=True, exact=False, sigmoid_mode=None,
               out_dtype=torch.float32, tables=None):
     """``sigmoid((G x_0 R[r] x_1 S[h]) . O^T)`` for a batch of (h, r) queries -> ``(B, N)``.
