@@ -32,32 +32,52 @@ static size_t packed_bytes(int dtype, int64_t batch, int c) {
     return (size_t)rtk_cdiv(batch, 32) * (size_t)rtk_pack_tile_bytes(ks, dtype == RTK_F32 ? 2 : 1);
 }
 
-static RtkWorkspace carve(void *base, int dtype, int64_t batch, int64_t n_rel, int a, int b, int c) {
-    RtkWorkspace w;
-    unsigned char *p = (unsigned char *)base;
+// Bump allocator over a caller-owned workspace: 256-byte steps; a null base only counts (size query).
+struct Carver {
+    unsigned char *base;
     size_t off = 0;
-    auto take = [&](size_t bytes) {
-        unsigned char *q = p ? p + off : nullptr;
+    void *take(size_t bytes) {
+        unsigned char *q = base ? base + off : nullptr;
         off += rtk_align_up(bytes, 256);
         return q;
-    };
+    }
+};
+
+// Scratch of the table build for `n_slots` tables (build_tables, rtk_query.hip); none at a <= 32 or for bf16 at a > 512.
+struct TablesWs {
+    void *core_t, *r_packed;
+    size_t total;   // bytes carved so far, the scratch included
+};
+static TablesWs tables_scratch(Carver &cv, int dtype, int64_t n_slots, int a, int b, int c) {
+    TablesWs s{nullptr, nullptr, 0};
+    if (dtype == RTK_BF16 && a > 32 && a <= 512) {   // bf16 MFMA score kernel: transposed core + packed relation rows
+        s.core_t = cv.take((size_t)a * b * c * 2);
+        s.r_packed = cv.take(packed_bytes(RTK_BF16, n_slots, a));
+    } else if (dtype == RTK_F32 && a > 32) {         // split-fp16 GEMM: operand bounds (256-byte header) + gathered relation rows
+        s.r_packed = cv.take(256 + (size_t)n_slots * a * 4);
+    }
+    s.total = cv.off;
+    return s;
+}
+
+static RtkWorkspace carve(void *base, int dtype, int64_t batch, int64_t n_rel, int a, int b, int c) {
+    RtkWorkspace w;
+    Carver cv{(unsigned char *)base};
     const int64_t n_u_max = n_rel > batch ? batch : n_rel;
-    w.flags = (uint32_t *)take(256);
-    w.slot_of_rel = (int32_t *)take((size_t)n_rel * 4);
-    w.rel_list = (int32_t *)take((size_t)n_u_max * 4);
-    w.tables = (float *)take((size_t)n_u_max * b * c * 4);
-    w.v = (float *)take((size_t)batch * c * 4);
-    w.q_packed = take(packed_bytes(dtype, batch, c));
-    const bool big_a = dtype == RTK_BF16 && a > 32 && a <= 512;   // tables through the bf16 MFMA kernel
-    w.core_t = big_a ? take((size_t)a * b * c * 2) : nullptr;
-    w.r_packed = big_a ? take(packed_bytes(RTK_BF16, n_u_max, a)) : nullptr;
-    // fp32, a > 32: tables through the split-fp16 GEMM -- operand bounds (256-byte header) + the gathered relation rows
-    if (dtype == RTK_F32 && a > 32) w.r_packed = take(256 + (size_t)n_u_max * a * 4);
-    w.grp_cnt = (int32_t *)take((size_t)n_u_max * 8);
-    w.grp_order = (int32_t *)take((size_t)batch * 4);
-    w.grp_work = (int32_t *)take((size_t)(batch / 4 + n_u_max + 1) * 16);
-    w.grp_qinfo = (int64_t *)take((size_t)batch * 16);
-    w.total = off;
+    w.flags = (uint32_t *)cv.take(256);
+    w.slot_of_rel = (int32_t *)cv.take((size_t)n_rel * 4);
+    w.rel_list = (int32_t *)cv.take((size_t)n_u_max * 4);
+    w.tables = (float *)cv.take((size_t)n_u_max * b * c * 4);
+    w.v = (float *)cv.take((size_t)batch * c * 4);
+    w.q_packed = cv.take(packed_bytes(dtype, batch, c));
+    const TablesWs ts = tables_scratch(cv, dtype, n_u_max, a, b, c);
+    w.core_t = ts.core_t;
+    w.r_packed = ts.r_packed;
+    w.grp_cnt = (int32_t *)cv.take((size_t)n_u_max * 8);
+    w.grp_order = (int32_t *)cv.take((size_t)batch * 4);
+    w.grp_work = (int32_t *)cv.take((size_t)(batch / 4 + n_u_max + 1) * 16);
+    w.grp_qinfo = (int64_t *)cv.take((size_t)batch * 16);
+    w.total = cv.off;
     return w;
 }
 
@@ -73,45 +93,23 @@ int rtk_from_tables_bf16_impl(const float *tables, int64_t n_rel, int b, int c, 
                               const int64_t *rel_idx, const int64_t *sub_idx, int64_t batch, float *v_out,
                               void *q_packed, const RtkWorkspace &ws, hipStream_t st, int rel_part = 0, int rel_parts = 1);
 
-// scratch of the tables build: only the bf16 large-relation-rank path needs any (transposed core, packed R rows)
-struct TablesWs {
-    void *core_t, *r_packed;
-    size_t total;
-};
+// workspace of rtk_relation_tables_*: header + the scratch of the table build, one table per relation
 static TablesWs carve_tables(void *base, int dtype, int64_t n_rel, int a, int b, int c) {
-    TablesWs w;
-    unsigned char *p = (unsigned char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        unsigned char *q = p ? p + off : nullptr;
-        off += rtk_align_up(bytes, 256);
-        return q;
-    };
-    (void)take(256);
-    const bool big_a = dtype == RTK_BF16 && a > 32 && a <= 512;
-    w.core_t = big_a ? take((size_t)a * b * c * 2) : nullptr;
-    w.r_packed = big_a ? take(packed_bytes(RTK_BF16, n_rel, a)) : nullptr;
-    if (dtype == RTK_F32 && a > 32) w.r_packed = take(256 + (size_t)n_rel * a * 4);   // (as in carve())
-    w.total = off;
-    return w;
+    Carver cv{(unsigned char *)base};
+    (void)cv.take(256);
+    return tables_scratch(cv, dtype, n_rel, a, b, c);
 }
 
 // workspace of rtk_query_vectors_from_tables_*: header + the slot order of the queries (slots = relation ids)
 static RtkWorkspace carve_ft(void *base, int64_t batch, int64_t n_rel) {
     RtkWorkspace w{};
-    unsigned char *p = (unsigned char *)base;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        unsigned char *q = p ? p + off : nullptr;
-        off += rtk_align_up(bytes, 256);
-        return q;
-    };
-    w.flags = (uint32_t *)take(256);
-    w.grp_cnt = (int32_t *)take((size_t)n_rel * 8);
-    w.grp_order = (int32_t *)take((size_t)batch * 4);
-    w.grp_work = (int32_t *)take((size_t)(batch / 4 + (n_rel < batch ? n_rel : batch) + 1) * 16);
-    w.grp_qinfo = (int64_t *)take((size_t)batch * 16);
-    w.total = off;
+    Carver cv{(unsigned char *)base};
+    w.flags = (uint32_t *)cv.take(256);
+    w.grp_cnt = (int32_t *)cv.take((size_t)n_rel * 8);
+    w.grp_order = (int32_t *)cv.take((size_t)batch * 4);
+    w.grp_work = (int32_t *)cv.take((size_t)(batch / 4 + (n_rel < batch ? n_rel : batch) + 1) * 16);
+    w.grp_qinfo = (int64_t *)cv.take((size_t)batch * 16);
+    w.total = cv.off;
     return w;
 }
 

@@ -342,15 +342,36 @@ __global__ __launch_bounds__(256) void pack_rel_rows_kernel(const rtk_bf16 *__re
                                                             unsigned char *__restrict__ planes, int ksteps) {
     const int n_u = n_u_dev ? min(n_u_max, (int)*n_u_dev) : n_u_max;
     const int u = blockIdx.x;                      // one relation slot per block (rows >= n_u: zeros)
-    unsigned char *tile = planes + (int64_t)(u >> 5) * rtk_pack_tile_bytes(ksteps, 1);
-    const int row = u & 31;
-    if (threadIdx.x == 0) reinterpret_cast<float *>(tile)[row] = 1.0f;
-    rtk_bf16 *plane = reinterpret_cast<rtk_bf16 *>(tile + RTK_PACK_HDR);
     int rel = 0;
     if (u < n_u) rel = rel_list ? rel_list[u] : u;
     rel = min(max(rel, 0), n_rel - 1);
-    for (int k = threadIdx.x; k < ksteps * 16; k += 256)
-        plane[rtk_pack_offset(ksteps, k, row)] = (u < n_u && k < a) ? R[(int64_t)rel * a + k] : (rtk_bf16)0;
+    rtk_pack_store_row_bf16(planes, u, ksteps, threadIdx.x, 256,
+                            [=](int k) { return (u < n_u && k < a) ? R[(int64_t)rel * a + k] : (rtk_bf16)0; });
+}
+
+// ---------------------------------------------- pieces of the contract kernels ------
+// Row bi of the table Mq, this thread's W columns at column slot `col` (one 16-byte load, or one float).  Each
+// contract kernel calls it LB times, under its own `bi < b` guard, before it uses the first row.
+template <bool VEC, int W>
+__device__ __forceinline__ void load_table_row(float (&x)[W], const float *Mq, int bi, int c, int col) {
+    if (VEC) {
+        const f32x4 y = *reinterpret_cast<const f32x4 *>(Mq + (int64_t)bi * c + col * 4);
+#pragma unroll
+        for (int j = 0; j < W; ++j) x[j] = y[j];
+    } else {
+        x[0] = Mq[(int64_t)bi * c + col];
+    }
+}
+
+// Maximum over the 256 threads in two halves with a __syncthreads() between them: every wave leaves its maximum in
+// red[wave * stride], then any thread reads the four.
+__device__ __forceinline__ void wave_max_put(float mx, float *red, int stride, int t) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((t & 63) == 0) red[(t >> 6) * stride] = mx;
+}
+__device__ __forceinline__ float wave_max_get(const float *red, int stride) {
+    return fmaxf(fmaxf(red[0], red[stride]), fmaxf(red[2 * stride], red[3 * stride]));
 }
 
 // ------------------------------------------------------------ contract ------
@@ -428,13 +449,7 @@ __global__ __launch_bounds__(256) void contract_kernel(const float *__restrict__
                     const int bi = b0 + k * gstep;
                     if (bi < b) {
                         sx[k] = rtk_to_f32(Sh[bi]);
-                        if (VEC) {
-                            const f32x4 y = *reinterpret_cast<const f32x4 *>(Mq + (int64_t)bi * c + col * 4);
-#pragma unroll
-                            for (int j = 0; j < W; ++j) x[k][j] = y[j];
-                        } else {
-                            x[k][0] = Mq[(int64_t)bi * c + col];
-                        }
+                        load_table_row<VEC, W>(x[k], Mq, bi, c, col);
                     }
                 }
 #pragma unroll
@@ -464,34 +479,12 @@ __global__ __launch_bounds__(256) void contract_kernel(const float *__restrict__
     }
     if (!q_packed) return;
     if (sizeof(T) == 2) {
-        // bf16 path: one plane of bf16 (round to nearest even), no scaling (bf16 has fp32's range)
-        unsigned char *tile = q_packed + (int64_t)(d >> 5) * rtk_pack_tile_bytes(ksteps, 1);
-        const int row = d & 31;
-        if (t == 0) reinterpret_cast<float *>(tile)[row] = 1.0f;
-        rtk_bf16 *plane = reinterpret_cast<rtk_bf16 *>(tile + RTK_PACK_HDR);
-        for (int k = t; k < ksteps * 16; k += 256) plane[rtk_pack_offset(ksteps, k, row)] = rtk_f32_to_bf16((k < c) ? part[k] : 0.f);
+        rtk_pack_store_row_bf16(q_packed, d, ksteps, part, c, t, 256);
         return;
     }
-    // row maximum -> power-of-two scale
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((t & 63) == 0) red[t >> 6] = mx;
+    wave_max_put(mx, red, 1, t);
     __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const int sh = rtk_pack_shift(mx);
-    const float up = ldexpf(1.0f, sh);
-    unsigned char *tile = q_packed + (int64_t)(d >> 5) * rtk_pack_tile_bytes(ksteps, 2);
-    const int row = d & 31;
-    if (t == 0) reinterpret_cast<float *>(tile)[row] = ldexpf(1.0f, -sh);
-    _Float16 *planes = reinterpret_cast<_Float16 *>(tile + RTK_PACK_HDR);
-    for (int k = t; k < ksteps * 16; k += 256) {
-        const float x = (k < c) ? part[k] * up : 0.f;
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        const int off = rtk_pack_offset(ksteps, k, row);
-        planes[off] = hi;
-        planes[off + ksteps * 512] = lo;  // plane 1 follows plane 0 (ksteps*2*32*8 halves)
-    }
+    rtk_pack_store_row_f32(q_packed, d, ksteps, part, c, wave_max_get(red, 1), t, 256);
 }
 
 // ---------------------------------------------------- grouped contract ------
@@ -565,15 +558,7 @@ __global__ __launch_bounds__(256) void contract_grouped_kernel(
 #pragma unroll
             for (int k = 0; k < LB; ++k) {
                 const int bi = b0 + k * ngroups;
-                if (bi < b) {
-                    if (VEC) {
-                        const f32x4 y = *reinterpret_cast<const f32x4 *>(Mq + (int64_t)bi * c + col * 4);
-#pragma unroll
-                        for (int j = 0; j < W; ++j) x[k][j] = y[j];
-                    } else {
-                        x[k][0] = Mq[(int64_t)bi * c + col];
-                    }
-                }
+                if (bi < b) load_table_row<VEC, W>(x[k], Mq, bi, c, col);
             }
 #pragma unroll
             for (int k = 0; k < LB; ++k) {
@@ -625,51 +610,20 @@ __global__ __launch_bounds__(256) void contract_grouped_kernel(
     if (!q_packed) return;
     if (sizeof(T) == 2) {   // bf16: one plane, round to nearest even, no scaling
         __syncthreads();
-        for (int q = 0; q < nq; ++q) {
-            const int d = qid[q];
-            unsigned char *tile = q_packed + (int64_t)(d >> 5) * rtk_pack_tile_bytes(ksteps, 1);
-            const int row = d & 31;
-            if (t == 0) reinterpret_cast<float *>(tile)[row] = 1.0f;
-            rtk_bf16 *plane = reinterpret_cast<rtk_bf16 *>(tile + RTK_PACK_HDR);
-            const float *rowv = part + q * PG * cpad;
-            for (int k = t; k < ksteps * 16; k += 256)
-                plane[rtk_pack_offset(ksteps, k, row)] = rtk_f32_to_bf16((k < c) ? rowv[k] : 0.f);
-        }
+        for (int q = 0; q < nq; ++q) rtk_pack_store_row_bf16(q_packed, qid[q], ksteps, part + q * PG * cpad, c, t, 256);
         return;
     }
 #pragma unroll
-    for (int q = 0; q < QG; ++q) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) mx[q] = fmaxf(mx[q], __shfl_xor(mx[q], o));
-        if ((t & 63) == 0) red[t >> 6][q] = mx[q];
-    }
+    for (int q = 0; q < QG; ++q) wave_max_put(mx[q], &red[0][q], QG, t);
     __syncthreads();
-    for (int q = 0; q < nq; ++q) {
-        const float m = fmaxf(fmaxf(red[0][q], red[1][q]), fmaxf(red[2][q], red[3][q]));
-        const int sh = rtk_pack_shift(m);
-        const float up = ldexpf(1.0f, sh);
-        const int d = qid[q];
-        unsigned char *tile = q_packed + (int64_t)(d >> 5) * rtk_pack_tile_bytes(ksteps, 2);
-        const int row = d & 31;
-        if (t == 0) reinterpret_cast<float *>(tile)[row] = ldexpf(1.0f, -sh);
-        _Float16 *planes = reinterpret_cast<_Float16 *>(tile + RTK_PACK_HDR);
-        const float *rowv = part + q * PG * cpad;
-        for (int k = t; k < ksteps * 16; k += 256) {
-            const float x = (k < c) ? rowv[k] * up : 0.f;
-            const _Float16 hi = (_Float16)x;
-            const _Float16 lo = (_Float16)(x - (float)hi);
-            const int off = rtk_pack_offset(ksteps, k, row);
-            planes[off] = hi;
-            planes[off + ksteps * 512] = lo;
-        }
-    }
+    for (int q = 0; q < nq; ++q)
+        rtk_pack_store_row_f32(q_packed, qid[q], ksteps, part + q * PG * cpad, c, wave_max_get(&red[0][q], QG), t, 256);
 }
 
 // ---------------------------------------------------------------- pack ------
 // Packed query planes from fp32 query vectors that were computed elsewhere (entity-sharded scoring with
-// stage 1 split over the ranks: the B x c vectors arrive by all-gather).  Same arithmetic as the tail of
-// the contract kernels: bf16 = round to nearest even, one plane; fp32 = row maximum -> power-of-two
-// scale -> fp16 hi/lo planes.  One workgroup per query row.
+// stage 1 split over the ranks: the B x c vectors arrive by all-gather), through the writers the contract
+// kernels use.  One workgroup per query row.
 template <bool BF16>
 __global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict__ v, int c, int ksteps,
                                                         unsigned char *__restrict__ q_packed) {
@@ -677,33 +631,15 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const float *__restrict_
     const int t = threadIdx.x;
     const int64_t d = blockIdx.x;
     const float *row = v + d * c;
-    unsigned char *tile = q_packed + (d >> 5) * rtk_pack_tile_bytes(ksteps, BF16 ? 1 : 2);
-    const int r = (int)(d & 31);
     if (BF16) {
-        if (t == 0) reinterpret_cast<float *>(tile)[r] = 1.0f;
-        rtk_bf16 *plane = reinterpret_cast<rtk_bf16 *>(tile + RTK_PACK_HDR);
-        for (int k = t; k < ksteps * 16; k += 256) plane[rtk_pack_offset(ksteps, k, r)] = rtk_f32_to_bf16((k < c) ? row[k] : 0.f);
+        rtk_pack_store_row_bf16(q_packed, d, ksteps, row, c, t, 256);
         return;
     }
     float mx = 0.f;
     for (int k = t; k < c; k += 256) mx = fmaxf(mx, fabsf(row[k]));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
-    if ((t & 63) == 0) red[t >> 6] = mx;
+    wave_max_put(mx, red, 1, t);
     __syncthreads();
-    mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const int sh = rtk_pack_shift(mx);
-    const float up = ldexpf(1.0f, sh);
-    if (t == 0) reinterpret_cast<float *>(tile)[r] = ldexpf(1.0f, -sh);
-    _Float16 *planes = reinterpret_cast<_Float16 *>(tile + RTK_PACK_HDR);
-    for (int k = t; k < ksteps * 16; k += 256) {
-        const float x = (k < c) ? row[k] * up : 0.f;
-        const _Float16 hi = (_Float16)x;
-        const _Float16 lo = (_Float16)(x - (float)hi);
-        const int off = rtk_pack_offset(ksteps, k, r);
-        planes[off] = hi;
-        planes[off + ksteps * 512] = lo;
-    }
+    rtk_pack_store_row_f32(q_packed, d, ksteps, row, c, wave_max_get(red, 1), t, 256);
 }
 
 // rows of R in table-slot order (slots past the batch's distinct relations hold an arbitrary valid row: never read)

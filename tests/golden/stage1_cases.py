@@ -35,18 +35,18 @@ SENTINEL = -777.25        # output rows nobody may write
 GARBAGE = 3.0             # table rows of slots past the batch's distinct relations
 PACK_FILL = 0xA5          # packed bytes nobody may write
 
-# ---- constants of the dispatch, with the line of csrc/rtk_query.hip each comes from ---------------------------
-GROUPS_LDS_SLOTS = 2048   # :54   counters in LDS up to this many slots
-CH = 8                    # :73   ids fetched per thread and trip; single = B <= NT * CH (:76)
-NT_HOSTED, NT_OWN = 256, 1024     # :209 / :295 build_groups<256> inside a host kernel, :192 groups_kernel
-UT = 4                    # :199  relations per workgroup of tables_kernel
-AB = 16                   # :217  relation-rank slices in flight in tables_kernel
-VALU_MAX_A = 32           # :743  a <= 32: VALU tables
-MFMA_MAX_A = 512          # rtk_abi.hip:51  bf16 MFMA tables up to this a (core_t / r_packed carved)
-LB = 8                    # :360  table rows requested per trip of the contract kernels
-GROUPED_MIN_B = 2048      # :808 / :813  QG = 8 and the grouped kernel from this batch size
-QG = 8                    # :808
-GROUPED_SMEM = 64 * 1024 - 1024   # :813
+# ---- constants of the dispatch, with the function or constant of csrc/rtk_query.hip each comes from ----------
+GROUPS_LDS_SLOTS = 2048   # GROUPS_LDS_SLOTS: counters in LDS up to this many slots
+CH = 8                    # build_groups_impl: CH, ids fetched per thread and trip; `single` = B <= NT * CH
+NT_HOSTED, NT_OWN = 256, 1024     # build_groups<256> in tables_kernel / transpose_core_kernel, <1024> in groups_kernel
+UT = 4                    # UT: relations per workgroup of tables_kernel
+AB = 16                   # tables_kernel: AB, relation-rank slices in flight
+VALU_MAX_A = 32           # build_tables: a <= 32, VALU tables
+MFMA_MAX_A = 512          # rtk_abi.hip tables_scratch: bf16 MFMA tables up to this a (core_t / r_packed carved)
+LB = 8                    # contract_kernel: LB, table rows requested per trip (contract_grouped_kernel: its own LB)
+GROUPED_MIN_B = 2048      # plan_contract: QG = 8 and the grouped kernel from this batch size
+QG = 8                    # plan_contract: QG
+GROUPED_SMEM = 64 * 1024 - 1024   # plan_contract: limit on smem_grouped
 
 
 @dataclass(frozen=True)
@@ -318,7 +318,7 @@ def packed_mismatch(got, v, dtype, fill=PACK_FILL, ref=None):
 
 # ------------------------------------------------------------------------------- dispatch mirror ------
 def plan_contract(b, c, B):
-    """(grouped, vec) of plan_contract (csrc/rtk_query.hip:799) for 16-byte-aligned tables."""
+    """(grouped, vec) of plan_contract (csrc/rtk_query.hip) for 16-byte-aligned tables."""
     vec = c % 4 == 0
     W = 4 if vec else 1
     cols = -(-c // W)
