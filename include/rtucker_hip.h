@@ -705,7 +705,8 @@ int rtk_score_topk_bf16(const void *q_packed, int64_t batch, int c, const void *
  *           rtk_score_candidates_bwd's ordered scatter builds (stable sort by entity, fixed chunk order).
  * max_pos: an upper bound, known to the host, on the number of CSR entries of the batch's queries (a query counted
  * as often as it occurs); the ordered scatter's buffers have that size.  More entries than that set bit 3 (value 8) of
- * the error word and the surplus is dropped.  rtk_bce_stream_rows_f32 needs no such bound (workspace for max_pos = 0).
+ * the error word and the surplus is dropped; below that the results do not depend on max_pos (the scatter's windows
+ * have a fixed size).  rtk_bce_stream_rows_f32 needs no such bound (workspace for max_pos = 0).
  * Workspace: rtk_bce_stream_workspace_bytes(batch, n_ent, c, max_pos), valid without a device, 256-byte aligned; with
  * cp = 32 * ceil(c / 32), S = splits and align256 rounding up to a multiple of 256:
  *     512 + align256(8 S batch) + align256(32 batch) + align256(4 S batch cp) + 2 align256(4 batch c)
@@ -779,7 +780,8 @@ int rtk_bce_stream_grad_o_part_f32(const void *q_packed, const float *v, int64_t
  *     lse_d    = log sum_j exp(z[d, j])                         (row maximum subtracted)
  *     loss     = (1 / B) sum_d ( w_d lse_d - sum_j y[d, j] z[d, j] )  = F.cross_entropy(z, y), mean reduction
  *     d loss / d z[d, j] = (w_d softmax(z_d)_j - y[d, j]) / B   (every column: there is no saturation rule)
- * pair_slot[d] < 0 is an empty list; entries outside [0, n_ent) are skipped.
+ * pair_slot[d] < 0 is an empty list; entries outside [0, n_ent) are skipped.  n_d is the STORED list length
+ * pair_ptr[s + 1] - pair_ptr[s]: a skipped entry adds no term but still counts in n_d (in 1 / n_d and in [n_d > 0]).
  *
  * Matrix form (rtk_ce.hip), on STORED fp32 logits Z (batch x n_ent, row pitch ld; any c -- what
  * rtk_score_*(flags without RTK_SCORE_SIGMOID) wrote):

@@ -554,7 +554,8 @@ int score_candidates(const char *fn, const float *v, int64_t batch, int c, const
 }
 
 // Flat front end of the ordered scatter (rtk_bce_stream.hip: the positives of a ragged CSR): M entries (entity ent[i],
-// query owner[i], logit gradient dz[i]); an entity outside [0, n_ent) adds nothing.  gO is zeroed, then written.
+// query owner[i], logit gradient dz[i]); an entity outside [0, n_ent) adds nothing.  gO is zeroed, then written.  The
+// bits of gO depend on the entries alone, not on how many surplus slots M leaves behind them.
 __global__ __launch_bounds__(256) void flat_keys_kernel(const int32_t *__restrict__ ent, int64_t n_ent, int64_t M,
                                                        int32_t *__restrict__ keys, int32_t *__restrict__ vals) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < M; i += (int64_t)gridDim.x * 256) {
@@ -668,7 +669,11 @@ int rtk_cand_flat_scatter(const char *fn, const int32_t *ent, const int32_t *own
         return RTK_ERR_LAUNCH;
     }
     if (m <= 0) return RTK_OK;
-    const CandWs ws = carve_cand(workspace, m, 1);
+    CandWs ws = carve_cand(workspace, m, 1);
+    // m is the caller's BOUND on the entries (the surplus slots sort last and add nothing): the sums must not depend on
+    // it, so the flat lists are always cut into windows of CAND_WIN, which P -- carved for cand_window(m) <= CAND_WIN -- holds
+    ws.win = CAND_WIN;
+    ws.nwin = rtk_cdiv(ws.M, ws.win);
     const unsigned gblocks = (unsigned)(rtk_cdiv(m, 256) < 4096 ? rtk_cdiv(m, 256) : 4096);
     hipLaunchKernelGGL(flat_keys_kernel, dim3(gblocks), dim3(256), 0, st, ent, n_ent, m, ws.keys[0], ws.vals[0]);
     return sorted_scatter(fn, ws, n_ent, dz, 1, 1, owner, v, c, gO, st);

@@ -136,6 +136,16 @@ def test_matrix_form_refusals(lib, which):
         assert rc == RTK_ERR_UNSUPPORTED and "65535" in err
 
 
+def test_matrix_form_size_limits(lib):
+    """One grid row per batch item in the gradient's launch; column indices are 32-bit."""
+    rc, err = _matrix(lib, "grad", batch=65536)
+    assert rc == RTK_ERR_UNSUPPORTED and "batch > 65535" in err
+    assert _matrix(lib, "rows", batch=65536, n_ent=0)[0] == RTK_ERR_BAD_ARG       # (the rows entry has no such limit)
+    for which in ("rows", "grad"):
+        rc, err = _matrix(lib, which, n_ent=1 << 31, ld=1 << 31)
+        assert rc == RTK_ERR_UNSUPPORTED and "dimension too large" in err, (which, rc, err)
+
+
 def test_symbols_bound(lib):
     for name in NAMES:
         assert name in _lib.SIGNATURES
