@@ -293,13 +293,12 @@ extern "C" int rtk_read_error_flag(void *workspace, void *stream, uint32_t *host
     hipStream_t st = (hipStream_t)stream;
     hipError_t e = hipMemcpyAsync(host_flag_out, workspace, 4, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    // clear on the SAME stream, behind the read: later launches on it start from a clean word
-    if (e == hipSuccess && *host_flag_out) e = hipMemsetAsync(workspace, 0, 4, st);
     if (e != hipSuccess) {
         rtk_set_error("rtk_read_error_flag: %s", hipGetErrorString(e));
         return RTK_ERR_LAUNCH;
     }
-    return RTK_OK;
+    // clear on the SAME stream, behind the read: later launches on it start from a clean word
+    return *host_flag_out ? rtk_zero_async("rtk_read_error_flag", workspace, 4, st) : RTK_OK;
 }
 
 static int check_common(const char *fn, const void *core, int a, int b, int c, const void *R, int64_t n_rel,

@@ -22,7 +22,7 @@
 //                 of X^T V.  A wave owns its 32 rows of gO: one read-add-store on top of the positives' share.
 //   pos_kernel    the positives: one workgroup per query re-scores the query's CSR entries with Frag (the sweeps' bits),
 //                 gives the loss correction -(1 - eps) (ln p - ln(1 - p)), the positives' share of dv, and the flat
-//                 (entity, query, dz) lists that the ordered scatter of rtk_candidates.hip turns into their share of gO.
+//                 (entity, query, dz) lists that the ordered scatter (rtk_scatter.h) turns into their share of gO.
 //
 // The block form (rtk_bce_stream_*_part_f32): O holds rows [col0, col0 + N) of an n_ent-row matrix.  The sweeps are
 // row-local, so they only take the smoothing term eps / n_ent from the host; pos_kernel owns the CSR entries whose
@@ -126,33 +126,12 @@ struct BceGo {
 
 // ---- host side -------------------------------------------------------------------------------------------------
 
-struct StreamWs {
-    size_t bounds, part_loss, rows_pos, slab, dvpos, vs, vp, off, ent, owner, dzf, sort, total;
+struct BceWs : StreamWs {
+    size_t part_loss;
 };
-StreamWs layout_of(int64_t batch, int c, int64_t max_pos) {
-    StreamWs L;
-    const int ks = (c + 15) / 16, nct = nct_of(ks);
-    const size_t B = (size_t)batch, S = (size_t)splits_of(batch), n_mt = (size_t)rtk_cdiv(batch, 32);
-    const size_t M = (size_t)(max_pos > 0 ? max_pos : 0);
-    size_t at = 256;                                          // [0, 256): the error word's header
-    auto take = [&](size_t bytes) {
-        const size_t p = at;
-        at += rtk_align_up(bytes, 256);
-        return p;
-    };
-    L.bounds = take(256);                                     // max |O|, max |s v|
-    L.part_loss = take(S * B * 8);
-    L.rows_pos = take(B * BS_POS_Y * 8);
-    L.slab = take(S * B * 32 * nct * 4);
-    L.dvpos = take(B * (size_t)c * 4);
-    L.vs = take(B * (size_t)c * 4);
-    L.vp = take(n_mt * (size_t)nct * 4096);
-    L.off = take((B + 1) * 4);
-    L.ent = take(M * 4);
-    L.owner = take(M * 4);
-    L.dzf = take(M * 4);
-    L.sort = take(rtk_cand_flat_workspace_bytes((int64_t)M));
-    L.total = at;
+BceWs layout_of(int64_t batch, int c, int64_t max_pos) {
+    BceWs L{stream_layout(batch, c, max_pos), 0};
+    L.part_loss = L.take((size_t)splits_of(batch) * (size_t)batch * 8);
     return L;
 }
 
@@ -160,12 +139,7 @@ StreamWs layout_of(int64_t batch, int c, int64_t max_pos) {
 int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, const float *O, int64_t n_local, int64_t col0,
                  int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos, float eps,
                  unsigned flags, const void *out, const void *workspace, size_t ws_bytes) {
-    const auto own = [&]() -> int {
-        RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
-        RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
-        RTK_REQUIRE(max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
-        return RTK_OK;
-    };
+    const auto own = [&] { return check_pos_eps(fn, max_pos, eps); };
     return check_block(fn, q_packed && pair_slot && pair_ptr && pair_obj && out, batch, c, O, n_local, col0, n_ent, own,
                        (1ll << 31) - 256, flags, "the loss is", workspace, ws_bytes,
                        [&] { return layout_of(batch, c, max_pos).total; });
@@ -174,7 +148,7 @@ int check_stream(const char *fn, const void *q_packed, int64_t batch, int c, con
 template <int KS, int SG>
 int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, int col0, int n_ent, const int64_t *slot,
                 const int64_t *ptr, const int64_t *obj, float eps, double *loss_rows, float *dv, unsigned char *ws,
-                const StreamWs &L, hipStream_t st, const char *fn) {
+                const BceWs &L, hipStream_t st, const char *fn) {
     const float t0 = eps / (float)n_ent, dt = 1.0f - eps;       // the smoothing term of the WHOLE entity count
     const int splits = splits_of(B), n_qg = (int)rtk_cdiv(rtk_cdiv(B, 32), BS_WAVES);
     float *bounds = reinterpret_cast<float *>(ws + L.bounds);
@@ -204,10 +178,9 @@ int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, in
 template <int KS, int SG>
 int launch_grad_o(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, int n_ent,
                   const int64_t *slot, const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps,
-                  const float *scale, float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
-    const GoWs G{L.bounds, L.vs, L.vp, L.off, L.ent, L.owner, L.dzf, L.sort};
+                  const float *scale, float *gO, unsigned char *ws, const BceWs &L, hipStream_t st, const char *fn) {
     return launch_go<KS, SG, BcePos>(qp, v, B, c, O, N, col0, slot, ptr, obj, max_pos, 1.0f - eps, scale,
-                                     BceGo{eps / (float)n_ent}, (const unsigned char *)nullptr, gO, ws, G, st, fn);
+                                     BceGo{eps / (float)n_ent}, (const unsigned char *)nullptr, gO, ws, L, st, fn);
 }
 
 // The two sweeps on rows [col0, col0 + n_local) of the (n_ent x c) matrix; the whole matrix is the block (0, n_ent).
@@ -217,7 +190,7 @@ int stream_rows(const char *fn, const void *q_packed, int64_t batch, int c, cons
     int rc = check_stream(fn, q_packed, batch, c, O, n_local, col0, n_ent, pair_slot, pair_ptr, pair_obj, 0, eps, flags,
                           loss_rows_out, workspace, ws_bytes);
     if (rc != RTK_OK || batch == 0) return rc;
-    const StreamWs L = layout_of(batch, c, 0);
+    const BceWs L = layout_of(batch, c, 0);
     return dispatch<float>(fn, c, flags, [&](auto K, auto SG) {
         return launch_rows<K.value, SG.value>((const unsigned char *)q_packed, (int)batch, c, O, (int)n_local, (int)col0,
                                               (int)n_ent, pair_slot, pair_ptr, pair_obj, eps, loss_rows_out, dv_out,
@@ -234,14 +207,8 @@ int stream_grad_o(const char *fn, const void *q_packed, const float *v, int64_t 
                           gO_out, workspace, ws_bytes);
     if (rc != RTK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (batch == 0) {                                         // no term touches any row
-        if (hipMemsetAsync(gO_out, 0, (size_t)n_local * c * 4, st) != hipSuccess) {
-            rtk_set_error("%s: memset failed", fn);
-            return RTK_ERR_LAUNCH;
-        }
-        return RTK_OK;
-    }
-    const StreamWs L = layout_of(batch, c, max_pos);
+    if (batch == 0) return zero_go(fn, gO_out, n_local, c, st);
+    const BceWs L = layout_of(batch, c, max_pos);
     return dispatch<float>(fn, c, flags, [&](auto K, auto SG) {
         return launch_grad_o<K.value, SG.value>((const unsigned char *)q_packed, v, (int)batch, c, O, (int)n_local, (int)col0,
                                                 (int)n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps, scale, gO_out,
@@ -252,8 +219,7 @@ int stream_grad_o(const char *fn, const void *q_packed, const float *v, int64_t 
 }  // namespace
 
 extern "C" size_t rtk_bce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
-    if (batch < 0 || n_ent < 1 || c < 1 || c > 16 * BS_MAX_KS || max_pos < 0 || max_pos >= (1ll << 31) - 1) return 0;
-    return layout_of(batch, c, max_pos).total;
+    return stream_shape_ok(batch, n_ent, c, max_pos) ? layout_of(batch, c, max_pos).total : 0;
 }
 
 extern "C" size_t rtk_bce_stream_part_workspace_bytes(int64_t batch, int64_t n_local, int c, int64_t max_pos) {

@@ -203,47 +203,22 @@ struct CeGo {
 
 // ---- host side -------------------------------------------------------------------------------------------------
 
-struct CeWs {
-    size_t bounds, part_max, part_sum, part_z, rows_pos, slab, dvpos, vs, vp, lw, off, ent, owner, dzf, sort, total;
+struct CeWs : StreamWs {
+    size_t part_max, part_sum, part_z, lw;
 };
 CeWs layout_of(int64_t batch, int c, int64_t max_pos) {
-    CeWs L;
-    const int ks = (c + 15) / 16, nct = nct_of(ks);
-    const size_t B = (size_t)batch, S = (size_t)splits_of(batch), n_mt = (size_t)rtk_cdiv(batch, 32);
-    const size_t M = (size_t)(max_pos > 0 ? max_pos : 0);
-    size_t at = 256;                                          // [0, 256): the error word's header
-    auto take = [&](size_t bytes) {
-        const size_t p = at;
-        at += rtk_align_up(bytes, 256);
-        return p;
-    };
-    L.bounds = take(256);                                     // max |O|, max |s v|
-    L.part_max = take(S * B * 4);
-    L.part_sum = take(S * B * 8);
-    L.part_z = take(S * B * 8);
-    L.rows_pos = take(B * BS_POS_Y * 8);
-    L.slab = take(S * B * 32 * nct * 4);
-    L.dvpos = take(B * (size_t)c * 4);
-    L.vs = take(B * (size_t)c * 4);
-    L.vp = take(n_mt * (size_t)nct * 4096);
-    L.lw = take(n_mt * 256);
-    L.off = take((B + 1) * 4);
-    L.ent = take(M * 4);
-    L.owner = take(M * 4);
-    L.dzf = take(M * 4);
-    L.sort = take(rtk_cand_flat_workspace_bytes((int64_t)M));
-    L.total = at;
+    CeWs L{stream_layout(batch, c, max_pos), 0, 0, 0, 0};
+    const size_t SB = (size_t)splits_of(batch) * (size_t)batch;
+    L.part_max = L.take(SB * 4);
+    L.part_sum = L.take(SB * 8);
+    L.part_z = L.take(SB * 8);
+    L.lw = L.take((size_t)rtk_cdiv(batch, 32) * 256);
     return L;
 }
 
 int check_ce(const char *fn, bool operands, int64_t batch, int c, const float *O, int64_t n_ent, int64_t max_pos, float eps,
              const void *workspace, size_t ws_bytes) {
-    const auto own = [&]() -> int {
-        RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
-        RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
-        RTK_REQUIRE(max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
-        return RTK_OK;
-    };
+    const auto own = [&] { return check_pos_eps(fn, max_pos, eps); };
     // (the entries take logits and have no flags: what = nullptr)
     return check_block(fn, operands, batch, c, O, n_ent, 0, n_ent, own, (1ll << 31) - 256, 0u, (const char *)nullptr, workspace,
                        ws_bytes, [&] { return layout_of(batch, c, max_pos).total; });
@@ -295,9 +270,8 @@ int launch_grad(const unsigned char *qp, const float *v, int B, int c, const flo
                            (const float *)slab, (const float *)dvpos, (const float *)bounds, dv);
     }
     if (!gO) return RTK_OK;
-    const GoWs G{L.bounds, L.vs, L.vp, L.off, L.ent, L.owner, L.dzf, L.sort};
     return launch_go<KS, CE_SG, CePos>(qp, v, B, c, O, N, 0, slot, ptr, obj, max_pos, dt, scale, CeGo{t0},
-                                       (const unsigned char *)lw, gO, ws, G, st, fn);
+                                       (const unsigned char *)lw, gO, ws, L, st, fn);
 }
 
 template <typename F>
@@ -309,8 +283,7 @@ int dispatch_ce(const char *fn, int c, F f) {
 }  // namespace
 
 extern "C" size_t rtk_ce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
-    if (batch < 0 || n_ent < 1 || c < 1 || c > 16 * BS_MAX_KS || max_pos < 0 || max_pos >= (1ll << 31) - 1) return 0;
-    return layout_of(batch, c, max_pos).total;
+    return stream_shape_ok(batch, n_ent, c, max_pos) ? layout_of(batch, c, max_pos).total : 0;
 }
 
 extern "C" int rtk_ce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
@@ -339,13 +312,7 @@ extern "C" int rtk_ce_stream_grad_f32(const void *q_packed, const float *v, int6
                       max_pos, label_smoothing, workspace, ws_bytes);
     if (rc != RTK_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (batch == 0) {                                         // no term touches any row
-        if (gO_out && hipMemsetAsync(gO_out, 0, (size_t)n_ent * c * 4, st) != hipSuccess) {
-            rtk_set_error("%s: memset failed", fn);
-            return RTK_ERR_LAUNCH;
-        }
-        return RTK_OK;
-    }
+    if (batch == 0) return zero_go(fn, gO_out, n_ent, c, st);
     const CeWs L = layout_of(batch, c, max_pos);
     return dispatch_ce(fn, c, [&](auto K) {
         return launch_grad<K.value>((const unsigned char *)q_packed, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr,

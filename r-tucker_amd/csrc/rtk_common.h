@@ -72,6 +72,13 @@ static inline int rtk_ensure_dynamic_lds(const void *kernel, int bytes, std::ato
     return RTK_ERR_LAUNCH;
 }
 
+static inline int rtk_zero_async(const char *fn, void *p, size_t bytes, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(p, 0, bytes, st);
+    if (e == hipSuccess) return RTK_OK;
+    rtk_set_error("%s: memset: %s", fn, hipGetErrorString(e));
+    return RTK_ERR_LAUNCH;
+}
+
 static inline size_t rtk_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int64_t rtk_cdiv(int64_t x, int64_t y) { return (x + y - 1) / y; }
 
@@ -88,6 +95,22 @@ static inline int rtk_dispatch_ksteps_(int ks, const char *what, F &f, std::inte
 template <int KMAX, typename F>
 static inline int rtk_dispatch_ksteps(int ks, const char *what, F &&f) {
     return rtk_dispatch_ksteps_(ks, what, f, std::make_integer_sequence<int, KMAX>{});
+}
+
+// Runtime (16-byte chunks per lane of a row, vector path) -> template arguments: f(integral_constant<int, nch>, bool
+// constant) for nch = 1 .. NMAX (NMAX = 2 or 4), instantiated for every pair.  Another nch launches nothing and is an
+// error: a row is never cut short.
+template <int NMAX, typename F>
+static inline int rtk_dispatch_chunks(const char *fn, int nch, bool vec, F &&f) {
+    auto by_vec = [&](auto nc) { vec ? f(nc, std::true_type{}) : f(nc, std::false_type{}); };
+    RTK_REQUIRE(nch >= 1 && nch <= NMAX, RTK_ERR_UNSUPPORTED, "%s: %d chunks per row, at most %d", fn, nch, NMAX);
+    if (nch == 1) by_vec(std::integral_constant<int, 1>{});
+    else if (nch == 2) by_vec(std::integral_constant<int, 2>{});
+    else if constexpr (NMAX == 4) {
+        if (nch == 3) by_vec(std::integral_constant<int, 3>{});
+        else by_vec(std::integral_constant<int, 4>{});
+    }
+    return rtk_check_launch(fn);
 }
 
 // Workspace layout (all offsets 256-B aligned), see rtk_abi.hip::ws_layout
@@ -128,6 +151,36 @@ __device__ __forceinline__ f32x4 rtk_load4(const rtk_bf16 *p) {
     r[2] = __builtin_bit_cast(float, w[1] << 16);
     r[3] = __builtin_bit_cast(float, w[1] & 0xffff0000u);
     return r;
+}
+// Element q of 16 bytes of a row held as four words (through a scalar: a bit_cast straight from the vector element
+// returned element 0 for every q)
+__device__ __forceinline__ float rtk_bits_elem(const u32x4 &w, int q, float) {
+    const unsigned x = w[q];
+    return __builtin_bit_cast(float, x);
+}
+__device__ __forceinline__ float rtk_bits_elem(const u32x4 &w, int q, rtk_bf16) {
+    const unsigned x = w[q >> 1];
+    return __builtin_bit_cast(float, (q & 1) ? (x & 0xffff0000u) : (x << 16));
+}
+// 16 bytes of row `row` at element j0 (4 fp32 / 8 bf16), zero past c.  VEC: the row is 16-B aligned and c % VW == 0.
+template <typename T, bool VEC>
+__device__ __forceinline__ u32x4 rtk_load_piece(const T *__restrict__ row, int j0, int c) {
+    if constexpr (VEC) {
+        if (j0 < c) return *reinterpret_cast<const u32x4 *>(row + j0);
+        return u32x4{0u, 0u, 0u, 0u};
+    }
+    u32x4 w{0u, 0u, 0u, 0u};
+    if constexpr (sizeof(T) == 4) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) w[q] = j0 + q < c ? __builtin_bit_cast(unsigned, (float)row[j0 + q]) : 0u;
+    } else {
+#pragma unroll
+        for (int q = 0; q < 8; ++q) {
+            const unsigned h = j0 + q < c ? (unsigned)row[j0 + q] : 0u;
+            w[q >> 1] |= (q & 1) ? (h << 16) : h;
+        }
+    }
+    return w;
 }
 template <typename T> __host__ __device__ constexpr int rtk_vec4_align() { return sizeof(T) == 4 ? 16 : 8; }
 // Correctly behaving fp32 logistic: 1/(1+exp(-x)) with ocml expf (<= 1 ulp) and an

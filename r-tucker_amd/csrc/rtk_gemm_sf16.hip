@@ -362,10 +362,8 @@ extern "C" int rtk_absmax_f32(const float *x, int64_t rows, int64_t cols, int64_
     RTK_REQUIRE(x && out, RTK_ERR_BAD_ARG, "rtk_absmax_f32: null pointer");
     RTK_REQUIRE(rows >= 0 && cols >= 0 && ld >= cols, RTK_ERR_BAD_ARG, "rtk_absmax_f32: bad shape");
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(out, 0, sizeof(float), st) != hipSuccess) {
-        rtk_set_error("rtk_absmax_f32: memset failed");
-        return RTK_ERR_LAUNCH;
-    }
+    const int rc = rtk_zero_async("rtk_absmax_f32", out, sizeof(float), st);
+    if (rc != RTK_OK) return rc;
     if (rows == 0 || cols == 0) return RTK_OK;
     if (ld == cols) { cols *= rows; ld = cols; rows = 1; }            // contiguous: one long row
     const bool vec = aligned16(x) && ld % 4 == 0;

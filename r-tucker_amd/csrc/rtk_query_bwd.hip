@@ -249,13 +249,8 @@ extern "C" int rtk_query_vectors_bwd_f32(const float *core, int a, int b, int c,
             rc = rtk_gemm_f32_ex(ws.X, 0, ab, nullptr, dv, 0, c, g_core, c, ab, c, batch, 0, nullptr, 0, st);
         if (rc != RTK_OK) return rc;
     }
-    hipError_t e = hipSuccess;
-    if (g_R) e = hipMemsetAsync(g_R, 0, (size_t)n_rel * a * 4, st);
-    if (e == hipSuccess && g_S) e = hipMemsetAsync(g_S, 0, (size_t)n_sub * b * 4, st);
-    if (e != hipSuccess) {
-        rtk_set_error("%s: memset: %s", fn, hipGetErrorString(e));
-        return RTK_ERR_LAUNCH;
-    }
+    if (g_R && (rc = rtk_zero_async(fn, g_R, (size_t)n_rel * a * 4, st)) != RTK_OK) return rc;
+    if (g_S && (rc = rtk_zero_async(fn, g_S, (size_t)n_sub * b * 4, st)) != RTK_OK) return rc;
     if (g_R || g_S)
         hipLaunchKernelGGL(scatter_rows_kernel, dim3((unsigned)(2 * batch)), dim3(256), 0, st, sub_idx, ws.rows_S, b, g_S, n_sub,
                            rel_idx, ws.rows_R, a, g_R, n_rel, (int)batch);

@@ -159,10 +159,8 @@ extern "C" int rtk_score_packed_bce_f32(const void *q_packed, int64_t batch, int
     RTK_REQUIRE(rtk_split_ksteps_supported(c), RTK_ERR_UNSUPPORTED, "rtk_score_packed_bce_f32: c=%d > 512 not supported", c);
     RTK_REQUIRE(label_smoothing >= 0.f && label_smoothing < 1.f, RTK_ERR_BAD_ARG, "rtk_score_packed_bce_f32: label smoothing %g outside [0, 1)", (double)label_smoothing);
     hipStream_t st = (hipStream_t)stream;
-    if (hipMemsetAsync(partials_out, 0, 512 * sizeof(double), st) != hipSuccess) {
-        rtk_set_error("rtk_score_packed_bce_f32: clearing the partial sums failed");
-        return RTK_ERR_LAUNCH;
-    }
+    const int zrc = rtk_zero_async("rtk_score_packed_bce_f32", partials_out, 512 * sizeof(double), st);
+    if (zrc != RTK_OK) return zrc;
     const int ks = (c + 15) / 16;
     const bool o_vec = (c % 4 == 0) && ((reinterpret_cast<uintptr_t>(O) & 15) == 0);
     const int B = (int)batch, N = (int)n_local;

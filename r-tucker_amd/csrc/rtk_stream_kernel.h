@@ -14,12 +14,8 @@
 #include "rtk_common.h"
 #include "rtk_pack.h"
 #include "rtk_score_rank_kernel.h"
+#include "rtk_scatter.h"
 #include "rtk_score_select.h"
-
-// the flat front end of the ordered scatter (rtk_candidates.hip)
-size_t rtk_cand_flat_workspace_bytes(int64_t m);
-int rtk_cand_flat_scatter(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m,
-                          int64_t n_ent, const float *v, int c, float *gO, void *workspace, hipStream_t st);
 
 namespace {
 
@@ -483,10 +479,51 @@ int splits_of(int64_t batch) {
 
 // ---- host side -------------------------------------------------------------------------------------------------
 
-// where sweep 2's launch sequence finds its pieces of the caller's workspace (byte offsets; [0, 4): the error word)
-struct GoWs {
-    size_t bounds, vs, vp, off, ent, owner, dzf, sort;        // bounds: max |s v| is its second float
+// The workspace pieces both losses use (byte offsets; [0, 256): the error word's header).  A loss takes its own partial
+// buffers behind them, so those offsets move with max_pos: a call fills what it reads, and nothing in the workspace but
+// the error word may be carried from one call (rows) to another (grad).  bounds: max |O|, max |s v|.
+struct StreamWs {
+    size_t bounds, rows_pos, slab, dvpos, vs, vp, off, ent, owner, dzf, sort, total;
+    size_t take(size_t bytes) {
+        const size_t p = total;
+        total += rtk_align_up(bytes, 256);
+        return p;
+    }
 };
+StreamWs stream_layout(int64_t batch, int c, int64_t max_pos) {
+    StreamWs L;
+    const int nct = nct_of((c + 15) / 16);
+    const size_t B = (size_t)batch, S = (size_t)splits_of(batch), n_mt = (size_t)rtk_cdiv(batch, 32);
+    const size_t M = (size_t)(max_pos > 0 ? max_pos : 0);
+    L.total = 256;
+    L.bounds = L.take(256);
+    L.rows_pos = L.take(B * BS_POS_Y * 8);
+    L.slab = L.take(S * B * 32 * nct * 4);
+    L.dvpos = L.take(B * (size_t)c * 4);
+    L.vs = L.take(B * (size_t)c * 4);
+    L.vp = L.take(n_mt * (size_t)nct * 4096);
+    L.off = L.take((B + 1) * 4);
+    L.ent = L.take(M * 4);
+    L.owner = L.take(M * 4);
+    L.dzf = L.take(M * 4);
+    L.sort = L.take(rtk_scatter_bytes((int64_t)M));
+    return L;
+}
+
+// what both losses require of max_pos and the label smoothing (check_block's `own`), the shapes for which their
+// *_workspace_bytes answer, and gO of an empty batch: no term touches any row
+int check_pos_eps(const char *fn, int64_t max_pos, float eps) {
+    RTK_REQUIRE(max_pos >= 0, RTK_ERR_BAD_ARG, "%s: max_pos = %lld must be >= 0", fn, (long long)max_pos);
+    RTK_REQUIRE(eps >= 0.f && eps < 1.f, RTK_ERR_BAD_ARG, "%s: label smoothing %g outside [0, 1)", fn, (double)eps);
+    RTK_REQUIRE(max_pos < (1ll << 31) - 1, RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
+    return RTK_OK;
+}
+bool stream_shape_ok(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
+    return batch >= 0 && n_ent >= 1 && c >= 1 && c <= 16 * BS_MAX_KS && max_pos >= 0 && max_pos < (1ll << 31) - 1;
+}
+int zero_go(const char *fn, float *gO, int64_t rows, int c, hipStream_t st) {
+    return gO ? rtk_zero_async(fn, gO, (size_t)rows * c * 4, st) : RTK_OK;
+}
 
 // Sweep 2 with everything before it, for the links LP (positives) and LK (sweep; qx: what travels with its query
 // tiles, LK::QB bytes each): vs = scale v and its packed images, the positives' flat lists (dt = 1 - eps) and the
@@ -494,7 +531,7 @@ struct GoWs {
 template <int KS, int SG, typename LP, typename LK>
 int launch_go(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, const int64_t *slot,
               const int64_t *ptr, const int64_t *obj, int64_t max_pos, float dt, const float *scale, LK lk,
-              const unsigned char *qx, float *gO, unsigned char *ws, const GoWs &L, hipStream_t st, const char *fn) {
+              const unsigned char *qx, float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
     constexpr int NCT = nct_of(KS);
     const int n_mt = (int)rtk_cdiv(B, 32);
     uint32_t *err = reinterpret_cast<uint32_t *>(ws);
@@ -517,7 +554,7 @@ int launch_go(const unsigned char *qp, const float *v, int B, int c, const float
         hipLaunchKernelGGL((pos_kernel<KS, SG, LP>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot,
                            ptr, obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
     }
-    rc = rtk_cand_flat_scatter(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
+    rc = rtk_scatter_flat(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
     if (rc != RTK_OK) return rc;
     // one workgroup per CU: whole entity tiles per slot, no query ranges
     const int n_slots = grid_of(B, N, RTK_N_CU).n_slots;
