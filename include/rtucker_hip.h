@@ -404,11 +404,16 @@ int rtk_comm_destroy(void *comm);
  *     A = D^-1 S D^-1 + (shift_diag + shift_trace * trace(S)) I = L L^T,
  * the upper triangular  R = L^T D  and  X = D^-1 L^-T :  W X has orthonormal columns, W = (W X) R, and
  * X X^T = (S + shift)^-1 when not equilibrated.  One workgroup per matrix, one launch, no workspace, no host
- * synchronisation, no failure status (a pivot that cancelled below 1e-14 of its diagonal entry is floored there;
- * trace(S) <= 0 gives zero outputs).  The Riemannian optimizer step orthonormalises and inverts the core's Gram
- * matrices with it (replaces tucker_riemopt's QR / SVD / solve calls reached from
+ * synchronisation, no failure status: a pivot that cancelled below  max(1e-14 of its diagonal entry of A, shift / 2)
+ * is floored there.  Only the lower triangle of S (diagonal included) is read.  trace(S) <= 0 or not a number, or a
+ * value that is not finite on or below the diagonal, gives zero R and X for that matrix (its neighbours in the batch
+ * are not affected).  Finite outputs are promised for positive semi-definite S plus rounding noise of the order of
+ * the floor, NOT for an indefinite S: behind a floored pivot the entries grow by 1 / sqrt(floor) per further floored
+ * column and overflow on a grossly indefinite matrix.  The Riemannian optimizer step orthonormalises and inverts the
+ * core's Gram matrices with it (replaces tucker_riemopt's QR / SVD / solve calls reached from
  * src/model/asymmetric/optim.py:86-89,107-108 and src/model/symmetric/optim.py:80-83,101-103).
- * The three buffers must be distinct.
+ * Refused before anything is enqueued, outputs untouched: a null operand, batch outside [1, 2^20), two of the three
+ * buffers equal, a negative shift (RTK_ERR_BAD_ARG); k outside [1, 256] (RTK_ERR_UNSUPPORTED).
  */
 int rtk_gram_factor_f64(const void *S, int64_t batch, int k, int equilibrate, double shift_diag, double shift_trace,
                         void *R_out, void *X_out, void *stream);

@@ -9,13 +9,26 @@
 // factorisation (32-wide blocks) on the matrix in its output buffer (L2-resident) with the
 // panel and the pivot rows of the inverse in LDS, and applies the same row operations to an identity, so
 // Linv falls out of the same sweep (no second triangular pass, no host round trip, no workspace): the
-// explicit inverse turns every "divide by L" of the step into a plain GEMM.  No failure path: a pivot that
+// explicit inverse turns every "divide by L" of the step into a plain GEMM.  No failure status: a pivot that
 // cancelled to (or below) half the diagonal shift (1e-14 of its original diagonal entry without a shift) is replaced by
 // that floor -- exact arithmetic on S >= 0 keeps every pivot above the shift, so the floor only acts on a Gram matrix
-// whose rounding noise exceeds it (an fp32 Gram matrix of 40 943 rows with dependent columns: noise 1e-5 against a
-// shift of 3e-6 gave pivots floored at 1e-14, L entries of 100 behind them and |L^-1| = 1e107) -- the callers
-// equilibrate and shift their matrices, so this only triggers on numerically rank-deficient input -- and
-// nothing is reported to the host (the training driver reads one health word per epoch).
+// whose rounding noise exceeds it -- the callers equilibrate and shift their matrices, so this only triggers on
+// numerically rank-deficient input -- and nothing is reported to the host (the training driver reads one health word
+// per epoch).
+//
+// What is promised (tests/test_gpu_chol_kernel.py, cases and bounds in tests/golden/chol_cases.py):
+//   * only the lower triangle of S (diagonal included) is read;
+//   * trace(S) <= 0 or not a number, or a value that is not finite on or under the diagonal: both outputs are zero;
+//   * S positive semi-definite plus rounding noise of the order of the floor: finite outputs, R[c][c] = sqrt(floor) D_c
+//     at a floored column, everything in front of the first floored column untouched;
+//   * NOT promised: finite output for an indefinite S.  Behind a floored pivot the entries are what cancelled divided by
+//     sqrt(floor); once they exceed the floor every later pivot is floored too and the entries grow by 1 / sqrt(floor)
+//     per column: k = 80 with one diagonal entry negated and a shift of 1e-6 floors 43 columns and overflows, and noise
+//     well above the shift does the same more slowly (an fp32 Gram matrix of 40 943 rows with dependent columns: noise
+//     1e-5 against a shift of 3e-6 gave pivots floored at 1e-14 by an earlier floor rule, L entries of 100 behind them
+//     and |L^-1| = 1e107).  The callers keep the noise under the shift (float64-accumulated Gram matrices,
+//     smalllinalg.tall_gram_f64); the CPU fallback of smalllinalg.gram_factor clamps eigenvalues and stays bounded on
+//     such input, so its tests say nothing about this kernel.
 //
 // Round 4 (513 -> 248 us per k = 200 matrix, 263 -> 127 us averaged over a training step's 25 launches;
 // profiles/r04_chol_phase_ablations.txt has the phase-by-phase ablations of the old form).  What the time was: with one
@@ -41,7 +54,8 @@ constexpr int IB = 8;         // loads in flight per thread in the copy-in / cop
 
 // S: k x k Gram matrix.  A = D^-1 S D^-1 + (shift_diag + shift_trace * trace(S)) I with D = sqrt(diag S) when
 // `equil` (else D = I) is factored A = L L^T; outputs (upper triangular)  R = L^T D  and  X = D^-1 L^-T, so that for
-// S = W^T W:  W X has orthonormal columns, W = (W X) R, and S^-1 ~ X X^T.  trace(S) <= 0: both outputs are zero.
+// S = W^T W:  W X has orthonormal columns, W = (W X) R, and S^-1 ~ X X^T.  trace(S) <= 0, or a value that is not finite
+// on or under the diagonal: both outputs are zero.  Nothing above the diagonal is read.
 // Lo / Ti are the output buffers, used as working storage (lower triangles) until the final transposition.
 __global__ __launch_bounds__(NT) void chol_inv_kernel(const double *__restrict__ S, int k, int equil, double shift_diag,
                                                       double shift_trace, double *__restrict__ Lo,
@@ -80,6 +94,9 @@ __global__ __launch_bounds__(NT) void chol_inv_kernel(const double *__restrict__
     const double shift = shift_diag + shift_trace * tr;
     // working copies: Lo = lower triangle of the scaled, shifted matrix (zero above), Ti = identity
     // (IB loads of a thread in flight together: one element per trip was k*k/1024 dependent trips to L2)
+    // A value that is not finite on or under the diagonal (the part that is read) makes the whole matrix dead: every
+    // thread keeps a flag over its own elements and the barrier that ends the pass ORs the flags.
+    int dead = 0;
     for (int e0 = t; e0 < k * k; e0 += IB * NT) {
         double sv[IB];
 #pragma unroll
@@ -93,13 +110,17 @@ __global__ __launch_bounds__(NT) void chol_inv_kernel(const double *__restrict__
             if (e < k * k) {
                 const int i = e / k, c = e - i * k;
                 const double a = sv[u] * idsc[i] * idsc[c] + ((c == i) ? shift : 0.0);
+                dead |= (c <= i) && !isfinite(sv[u]);
                 Lo[e] = (c <= i) ? a : 0.0;
                 Ti[e] = (c == i) ? 1.0 : 0.0;
                 if (c == i) dg[i] = a;
             }
         }
     }
-    __syncthreads();
+    if (__syncthreads_or(dead)) {            // zero outputs (a thread overwrites the elements it wrote above)
+        for (int e = t; e < k * k; e += NT) Lo[e] = 0.0, Ti[e] = 0.0;
+        return;
+    }
     const int r = t >> 5, cc = t & 31;       // (row, column) inside a 32 x 32 block
     for (int j0 = 0; j0 < k; j0 += NB) {
         const int w = min(NB, k - j0);

@@ -13,7 +13,8 @@ tensor), so no Rayleigh-Ritz step and no eigenvalues are required.
 ``gram_factor`` is the only factorisation: on the GPU it is one launch of ``rtk_gram_factor_f64`` (batched, one
 workgroup per matrix, equilibration + shift + Cholesky + inverse + transposed outputs fused, csrc/rtk_chol.hip);
 elsewhere (CPU tests) ``torch.linalg.cholesky_ex`` + ``solve_triangular``.  A failed factorisation cannot raise (that would need a sync): pivots are kept positive by a
-relative diagonal shift, and the training driver reads one device-side health word per epoch.
+relative diagonal shift and a floor (finite output for positive semi-definite input plus rounding noise, not for an
+indefinite matrix), and the training driver reads one device-side health word per epoch.
 """
 from __future__ import annotations
 
@@ -37,7 +38,14 @@ def gram_factor(S: torch.Tensor, shift: float = None, equilibrate: bool = True, 
     Cholesky's accuracy depends on the condition number of the SCALED matrix; ``D = I`` if not ``equilibrate``) and
     ``L`` the Cholesky factor of ``D^-1 S D^-1 + (shift + shift_trace * trace S) I``,  ``X = D^-1 L^-T`` and
     ``R = L^T D``.  Not equilibrated, ``X X^T = (S + shift)^-1``.  A zero column stays zero; a zero matrix gives
-    zeros.  On the GPU: ONE launch of ``rtk_gram_factor_f64`` (csrc/rtk_chol.hip) for k <= 256."""
+    zeros.  On the GPU: ONE launch of ``rtk_gram_factor_f64`` (csrc/rtk_chol.hip) for k <= 256.
+
+    The contract, the same on both paths (tests/test_gpu_chol_kernel.py, tests/test_smalllinalg.py): only the lower
+    triangle of ``S`` is read; a non-finite value on or below the diagonal, or a trace that is not positive, gives
+    zero ``X`` and ``R``.  Finite output is promised for a positive semi-definite ``S`` plus rounding noise (a pivot
+    that cancels is floored at half the shift), NOT for an indefinite ``S``: behind a floored pivot the kernel's
+    entries grow by ``1 / sqrt(floor)`` per further floored column and overflow on a grossly indefinite matrix (the
+    CPU fallback clamps eigenvalues and stays bounded there, so it says nothing about the kernel)."""
     k = S.shape[-1]
     sh = SHIFT[torch.float64] if shift is None else float(shift)
     S64 = S.double()
@@ -53,14 +61,17 @@ def gram_factor(S: torch.Tensor, shift: float = None, equilibrate: bool = True, 
                                                R.data_ptr(), X.data_ptr(), torch.cuda.current_stream(S.device).cuda_stream),
                        "rtk_gram_factor_f64")
         return X, R
-    # CPU / large-k fallback with the HIP kernel's no-failure semantics (csrc/rtk_chol.hip): a matrix whose trace is
-    # zero or not finite gives zero outputs; a pivot that cancelled (an indefinite or inconsistent Gram matrix) is
-    # floored at half the shift instead of failing -- here by clamping the eigenvalues of the equilibrated, shifted
-    # matrix, which leaves a positive definite input untouched to rounding
-    S64 = torch.where(torch.isfinite(S64), S64, torch.zeros_like(S64))
+    # CPU / large-k fallback with the HIP kernel's contract (csrc/rtk_chol.hip): only the lower triangle is read; a
+    # matrix whose trace is not positive, or with a non-finite value on or below its diagonal, gives zero outputs; a
+    # pivot that cancelled (a Gram matrix whose rounding noise exceeds the shift) is floored at half the shift instead
+    # of failing -- here by clamping the eigenvalues of the equilibrated, shifted matrix, which leaves a positive
+    # definite input untouched to rounding (and, unlike the kernel's floor, stays bounded on an indefinite input)
+    low = S64.tril()
+    ok = torch.isfinite(low).all(-1).all(-1)
+    low = torch.where(torch.isfinite(low), low, torch.zeros_like(low))
+    S64 = low + low.tril(-1).transpose(-1, -2)
     diag = S64.diagonal(dim1=-2, dim2=-1)
     tr = diag.sum(-1)
-    ok = torch.isfinite(S.double().reshape(*S.shape[:-2], -1).sum(-1))
     live = ((tr > 0) & ok).to(torch.float64)
     if equilibrate:
         d = torch.sqrt(torch.clamp(diag, min=0.0))

@@ -272,21 +272,31 @@ def test_cholesky_qr_of_a_rank_deficient_fp32_block_cpu():
 
 
 def test_gram_factor_has_no_failure_path_on_the_cpu_either():
-    """The CPU fallback mirrors the HIP kernel (csrc/rtk_chol.hip): an INDEFINITE "Gram" matrix (a pivot cancels) is
-    floored instead of failing, a non-finite one gives zero outputs; a positive definite one is untouched."""
+    """The CPU fallback and the HIP kernel (csrc/rtk_chol.hip) have one contract for non-finite input, tested on the
+    device by tests/test_gpu_chol_kernel.py::test_non_finite_input: a non-finite value on or below the diagonal gives
+    zero outputs, entries above the diagonal are not read; a positive definite matrix is untouched.  The fallback also
+    stays bounded on an INDEFINITE "Gram" matrix (it clamps eigenvalues) -- that is outside the kernel's contract
+    (positive semi-definite plus rounding noise) and says nothing about the kernel."""
     torch.manual_seed(3)
     k = 12
     A = torch.randn(40, k, dtype=torch.float64)
     good = A.T @ A
     bad = good.clone()
     bad[3, 3] = -0.5 * good[3, 3]                       # indefinite: plain Cholesky breaks down here
-    nan = good.clone()
-    nan[5, 7] = float("nan")
-    X, R = sl.gram_factor(torch.stack([good, bad, nan]))
+    nan_low, inf_diag, nan_up = good.clone(), good.clone(), good.clone()
+    nan_low[7, 5] = float("nan")
+    inf_diag[3, 3] = float("inf")
+    nan_up[5, 7] = float("nan")                         # above the diagonal: never read
+    X, R = sl.gram_factor(torch.stack([good, bad, nan_low, inf_diag, nan_up, good]))
     assert torch.isfinite(X).all() and torch.isfinite(R).all()
-    assert torch.equal(X[2], torch.zeros_like(X[2])) and torch.equal(R[2], torch.zeros_like(R[2]))
-    Xg, Rg = sl.gram_factor(good)
+    for dead in (2, 3):
+        assert torch.equal(X[dead], torch.zeros_like(X[dead])) and torch.equal(R[dead], torch.zeros_like(R[dead]))
+    for same in (4, 5):                                 # the ignored NaN and the dead ones' neighbour: the clean bits
+        assert torch.equal(X[same], X[0]) and torch.equal(R[same], R[0]), same
+    Xg, Rg = sl.gram_factor(good)                       # (alone no eigenvalue is clamped: equal to rounding)
     assert torch.allclose(X[0], Xg) and torch.allclose(R[0], Rg)
+    Xu, Ru = sl.gram_factor(nan_up)
+    assert torch.equal(Xu, Xg) and torch.equal(Ru, Rg)
     # the good one is a Cholesky-QR step: (A X) has orthonormal columns up to the shift
     Q = A @ X[0]
     assert (Q.T @ Q - torch.eye(k, dtype=torch.float64)).abs().max() < 1e-5
