@@ -845,6 +845,54 @@ int rtk_ce_stream_grad_f32(const void *q_packed, const float *v, int64_t batch, 
                            int64_t max_pos, float label_smoothing, const float *lse, const float *scale,
                            float *dv_out, float *gO_out, void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * The same loss on one block of entity rows (an entity shard): the caller holds rows [col0, col0 + n_local) of the
+ * (n_ent x c) entity matrix as O_local; pair_obj holds GLOBAL entity ids (the conventions of rtk_bce_stream_*_part_f32).
+ * Unlike the BCE loss this one is NOT a sum over entities: the row's log-sum-exp couples the blocks.  So the forward
+ * stops before the logarithm and the backward takes the lse of the WHOLE row from the caller:
+ *   rtk_ce_stream_rows_part_f32  the block's partial state of every query d, j over the block's rows only:
+ *                                  max_out[d]    = m = max_j z[d, j]                              (float)
+ *                                  sumexp_out[d] = sum_j exp(z[d, j] - m)                         (float64, >= 1)
+ *                                  lin_out[d]    = -t0 sum_j z[d, j]
+ *                                                  - (1 - eps) / n_d sum_{t in P_d, t in block} z[d, t]   (float64)
+ *                                with t0 = eps / n_ent, the GLOBAL entity count, and n_d the GLOBAL (stored) list
+ *                                length.  The sweep and the positives are those of rtk_ce_stream_rows_f32; the
+ *                                `splits` partials are merged in range order in float64 as there, without the
+ *                                logarithm.  Over a partition of [0, n_ent) into blocks k the caller forms
+ *                                  M = max_k m_k,  lse_d = M + log sum_k s_k exp(m_k - M)   (MAX, then SUM over ranks),
+ *                                  loss_rows[d] = w_d lse_d + sum_k lin_k[d]                (SUM),
+ *                                which is rtk_ce_stream_rows_f32's loss_rows_out up to the order of the float64 sums.
+ *   rtk_ce_stream_grad_part_f32  rtk_ce_stream_grad_f32 on the block, given the GLOBAL lse (batch floats):
+ *                                x[d, j] = w_d exp(z[d, j] - lse[d]) - eps / n_ent;
+ *                                dv_out[d, :] = sum_{j in block} x[d, j] O_local[j, :] is the block's share (unscaled;
+ *                                all-reduce SUM over the ranks completes it, batch x c floats, before
+ *                                rtk_query_vectors_bwd_f32); gO_local_out (n_local x c) holds the block's rows of gO,
+ *                                written in full, no exchange.  Either output may be NULL.
+ * With col0 = 0 and n_local = n_ent, grad_part has the bits of rtk_ce_stream_grad_f32 (that entry point IS this block),
+ * and max_out + log(sumexp_out), w lse + lin_out are rtk_ce_stream_rows_f32's lse and loss rows up to the last
+ * rounding.  A CSR entry e belongs to the block iff col0 <= e < col0 + n_local (local row e - col0); the others are
+ * skipped in lin_out, in the positives' share of dv and in the ordered scatter's lists, where they keep their slot
+ * with the "adds nothing" key: the launch sequence depends on batch, c, n_local and max_pos only (static,
+ * graph-capturable).  max_pos bounds the CSR entries of the batch's queries in ALL blocks.  The O-wide power of two of
+ * the dv product comes from the block's own rows.  Element arithmetic, summation orders within the block, the error
+ * word, covered range and refusals as rtk_ce_stream_*; in addition col0 < 0, n_local < 1 or col0 + n_local > n_ent
+ * give RTK_ERR_BAD_ARG before anything is enqueued.  No float atomics; repeated calls give the same bits.
+ * batch == 0: rows_part returns at once, grad_part zeroes gO_local_out.
+ * Workspace: rtk_ce_stream_part_workspace_bytes(batch, n_local, c, max_pos) (rows_part: max_pos = 0), valid without a
+ * device, 256-byte aligned, first word the error word; the formula of rtk_ce_stream_workspace_bytes: n_local does not
+ * enter, nothing grows with batch * n_local.
+ */
+size_t rtk_ce_stream_part_workspace_bytes(int64_t batch, int64_t n_local, int c, int64_t max_pos);
+int rtk_ce_stream_rows_part_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                                int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                const int64_t *pair_obj, float label_smoothing, float *max_out, double *sumexp_out,
+                                double *lin_out, void *workspace, size_t ws_bytes, void *stream);
+int rtk_ce_stream_grad_part_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O_local,
+                                int64_t n_local, int64_t col0, int64_t n_ent, const int64_t *pair_slot,
+                                const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos, float label_smoothing,
+                                const float *lse, const float *scale, float *dv_out, float *gO_local_out,
+                                void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

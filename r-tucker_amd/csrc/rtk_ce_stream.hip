@@ -10,10 +10,19 @@
 //
 //   ce_fwd_kernel    the forward, sweep 1 without the second tile product: each lane keeps an online (maximum, sum of
 //                    exp) and the sum of z of its query over its 16 entities per tile; partials per split.
-//   ce_finish_kernel merges the splits' partials in split order in float64, adds the positives' term (pos_kernel with
-//                    the CE link) and gives loss_rows and lse.
+//   ce_finish_kernel merges the splits' partials in split order in float64 (ce_merge_splits), adds the positives' term
+//                    (pos_kernel with the CE link) and gives loss_rows and lse.
 //   ce_dv_kernel     backward sweep 1 with the second tile product: dv[d, :] = sum_j x[d, j] O[j, :].
 //   go_kernel        backward sweep 2 with the CE link: the tile's 32 values of lse and w travel with the query tile.
+//
+// The block form (rtk_ce_stream_*_part_f32): O holds rows [col0, col0 + N) of an n_ent-row matrix.  The loss is NOT a
+// sum over entities -- the row's log-sum-exp couples the blocks -- so the forward stops before the logarithm and gives
+// the block's (maximum, sum of exp at that maximum, linear part); the caller merges the blocks and hands the GLOBAL lse
+// to the backward, which is the whole-matrix backward on the block's rows (t0 = eps / n_ent, n_d the stored list length,
+// pos_kernel owning the CSR entries whose global id falls into the block).  The whole-matrix gradient entry point is
+// the block launcher with col0 = 0, N = n_ent.
+//
+//   ce_part_finish_kernel  the same merge of the splits (ce_merge_splits), without the logarithm and without w.
 //
 // Every sum has a fixed order; no float atomics; nothing grows with B x N.
 #include "rtk_stream_kernel.h"
@@ -127,8 +136,27 @@ __global__ __launch_bounds__(64 * BS_WAVES, 1) void ce_dv_kernel(const unsigned 
     rows_sweep<KS, CE_SG, true>(pol, qp, B, O, N, c, o_bound, n_splits, slab);
 }
 
-// The splits' partials in split order, in float64: lse_d = M + ln sum_k S_k exp(M_k - M) (a split without a tile has
-// S_k = 0), then loss_rows[d] = w_d lse_d - t0 sum_k SZ_k + the positives' term.  One thread per query.
+// The splits' partials of query d in split order, in float64: the maximum m, s = sum_k S_k exp(M_k - m) (a split
+// without a tile has S_k = 0), sz = sum_k SZ_k, and the positives' term pcor.
+__device__ __forceinline__ void ce_merge_splits(int d, int B, int n_splits, const float *__restrict__ part_max,
+                                                const double *__restrict__ part_sum, const double *__restrict__ part_z,
+                                                const double *__restrict__ rows_pos, float &m, double &s, double &sz,
+                                                double &pcor) {
+    m = CE_NONE;
+    for (int k = 0; k < n_splits; ++k) m = fmaxf(m, part_max[(int64_t)k * B + d]);
+    s = sz = 0.0;
+    for (int k = 0; k < n_splits; ++k) {
+        const int64_t at = (int64_t)k * B + d;
+        const double sk = part_sum[at];
+        if (sk > 0.0) s += sk * exp((double)part_max[at] - (double)m);
+        sz += part_z[at];
+    }
+    pcor = 0.0;
+#pragma unroll
+    for (int u = 0; u < BS_POS_Y; ++u) pcor += rows_pos[(int64_t)d * BS_POS_Y + u];
+}
+
+// lse_d = m + ln s, then loss_rows[d] = w_d lse_d - t0 sz + the positives' term.  One thread per query.
 __global__ __launch_bounds__(256) void ce_finish_kernel(int B, int n_splits, double t0, double eps,
                                                         const float *__restrict__ part_max,
                                                         const double *__restrict__ part_sum,
@@ -139,22 +167,32 @@ __global__ __launch_bounds__(256) void ce_finish_kernel(int B, int n_splits, dou
                                                         double *__restrict__ loss_rows, float *__restrict__ lse_out) {
     const int d = blockIdx.x * 256 + threadIdx.x;
     if (d >= B) return;
-    float m = CE_NONE;
-    for (int k = 0; k < n_splits; ++k) m = fmaxf(m, part_max[(int64_t)k * B + d]);
-    double s = 0.0, sz = 0.0;
-    for (int k = 0; k < n_splits; ++k) {
-        const int64_t at = (int64_t)k * B + d;
-        const double sk = part_sum[at];
-        if (sk > 0.0) s += sk * exp((double)part_max[at] - (double)m);
-        sz += part_z[at];
-    }
+    float m;
+    double s, sz, pcor;
+    ce_merge_splits(d, B, n_splits, part_max, part_sum, part_z, rows_pos, m, s, sz, pcor);
     const double lse = (double)m + log(s);
-    double pcor = 0.0;
-#pragma unroll
-    for (int u = 0; u < BS_POS_Y; ++u) pcor += rows_pos[(int64_t)d * BS_POS_Y + u];
     const double w = (ce_list_len(d, pair_slot, pair_ptr) > 0 ? 1.0 - eps : 0.0) + eps;
     loss_rows[d] = w * lse - t0 * sz + pcor;
     lse_out[d] = (float)lse;
+}
+
+// The block form of ce_finish_kernel, stopped before the logarithm (the block does not know the other blocks):
+// max_out[d] = m, sumexp_out[d] = s, lin_out[d] = -t0 sz + the positives' term of the block's entries.
+__global__ __launch_bounds__(256) void ce_part_finish_kernel(int B, int n_splits, double t0,
+                                                             const float *__restrict__ part_max,
+                                                             const double *__restrict__ part_sum,
+                                                             const double *__restrict__ part_z,
+                                                             const double *__restrict__ rows_pos,
+                                                             float *__restrict__ max_out, double *__restrict__ sumexp_out,
+                                                             double *__restrict__ lin_out) {
+    const int d = blockIdx.x * 256 + threadIdx.x;
+    if (d >= B) return;
+    float m;
+    double s, sz, pcor;
+    ce_merge_splits(d, B, n_splits, part_max, part_sum, part_z, rows_pos, m, s, sz, pcor);
+    max_out[d] = m;
+    sumexp_out[d] = s;
+    lin_out[d] = -t0 * sz + pcor;
 }
 
 // lw of query tile mt: lse of its 32 queries, then their w; queries past B carry zeros
@@ -216,40 +254,48 @@ CeWs layout_of(int64_t batch, int c, int64_t max_pos) {
     return L;
 }
 
-int check_ce(const char *fn, bool operands, int64_t batch, int c, const float *O, int64_t n_ent, int64_t max_pos, float eps,
-             const void *workspace, size_t ws_bytes) {
+int check_ce(const char *fn, bool operands, int64_t batch, int c, const float *O, int64_t n_local, int64_t col0, int64_t n_ent,
+             int64_t max_pos, float eps, const void *workspace, size_t ws_bytes) {
     const auto own = [&] { return check_pos_eps(fn, max_pos, eps); };
     // (the entries take logits and have no flags: what = nullptr)
-    return check_block(fn, operands, batch, c, O, n_ent, 0, n_ent, own, (1ll << 31) - 256, 0u, (const char *)nullptr, workspace,
-                       ws_bytes, [&] { return layout_of(batch, c, max_pos).total; });
+    return check_block(fn, operands, batch, c, O, n_local, col0, n_ent, own, (1ll << 31) - 256, 0u, (const char *)nullptr,
+                       workspace, ws_bytes, [&] { return layout_of(batch, c, max_pos).total; });
 }
 
+// The forward on rows [col0, col0 + N) of the (n_ent x c) matrix.  The whole matrix (col0 = 0, N = n_ent) ends in
+// ce_finish_kernel (loss_rows, lse); a block (part_max_out given) in ce_part_finish_kernel (maximum, sum of exp, linear part).
 template <int KS>
-int launch_fwd(const unsigned char *qp, int B, int c, const float *O, int N, const int64_t *slot, const int64_t *ptr,
-               const int64_t *obj, float eps, double *loss_rows, float *lse, unsigned char *ws, const CeWs &L,
-               hipStream_t st) {
+int launch_fwd(const unsigned char *qp, int B, int c, const float *O, int N, int col0, int n_ent, const int64_t *slot,
+               const int64_t *ptr, const int64_t *obj, float eps, double *loss_rows, float *lse, float *part_max_out,
+               double *part_sumexp_out, double *part_lin_out, unsigned char *ws, const CeWs &L, hipStream_t st) {
     const int splits = splits_of(B), n_qg = (int)rtk_cdiv(rtk_cdiv(B, 32), BS_WAVES);
     float *part_max = reinterpret_cast<float *>(ws + L.part_max);
     double *part_sum = reinterpret_cast<double *>(ws + L.part_sum), *part_z = reinterpret_cast<double *>(ws + L.part_z);
     double *rows_pos = reinterpret_cast<double *>(ws + L.rows_pos);
-    hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, 0, c,
+    hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c,
                        1.0f - eps, slot, ptr, obj, rows_pos, (float *)nullptr, (const int32_t *)nullptr, (int64_t)0,
                        (int32_t *)nullptr, (int32_t *)nullptr, (float *)nullptr);
     constexpr int bytes = RowsLds<KS>::TOTAL;
     static_assert(bytes <= 64 * 1024, "ce_fwd_kernel: one 32-row tile in two layouts fits the default LDS limit");
     RTK_LAUNCH_SCORE((ce_fwd_kernel<KS>), dim3((unsigned)(n_qg * splits)), dim3(64 * BS_WAVES), bytes, st, qp, B, O, N, c,
                      splits, part_max, part_sum, part_z);
-    hipLaunchKernelGGL(ce_finish_kernel, dim3((unsigned)rtk_cdiv(B, 256)), dim3(256), 0, st, B, splits,
-                       (double)eps / (double)N, (double)eps, (const float *)part_max, (const double *)part_sum,
-                       (const double *)part_z, (const double *)rows_pos, slot, ptr, loss_rows, lse);
+    const double t0 = (double)eps / (double)n_ent;               // the smoothing term of the WHOLE entity count
+    if (part_max_out)
+        hipLaunchKernelGGL(ce_part_finish_kernel, dim3((unsigned)rtk_cdiv(B, 256)), dim3(256), 0, st, B, splits, t0,
+                           (const float *)part_max, (const double *)part_sum, (const double *)part_z,
+                           (const double *)rows_pos, part_max_out, part_sumexp_out, part_lin_out);
+    else
+        hipLaunchKernelGGL(ce_finish_kernel, dim3((unsigned)rtk_cdiv(B, 256)), dim3(256), 0, st, B, splits, t0, (double)eps,
+                           (const float *)part_max, (const double *)part_sum, (const double *)part_z,
+                           (const double *)rows_pos, slot, ptr, loss_rows, lse);
     return RTK_OK;
 }
 
 template <int KS>
-int launch_grad(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, const int64_t *slot,
-                const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps, const float *lse, const float *scale,
-                float *dv, float *gO, unsigned char *ws, const CeWs &L, hipStream_t st, const char *fn) {
-    const float t0 = eps / (float)N, dt = 1.0f - eps;
+int launch_grad(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, int n_ent,
+                const int64_t *slot, const int64_t *ptr, const int64_t *obj, int64_t max_pos, float eps, const float *lse,
+                const float *scale, float *dv, float *gO, unsigned char *ws, const CeWs &L, hipStream_t st, const char *fn) {
+    const float t0 = eps / (float)n_ent, dt = 1.0f - eps;        // the smoothing term of the WHOLE entity count
     constexpr int NCT = nct_of(KS);
     const int n_mt = (int)rtk_cdiv(B, 32), splits = splits_of(B), n_qg = (int)rtk_cdiv(n_mt, BS_WAVES);
     float *bounds = reinterpret_cast<float *>(ws + L.bounds);
@@ -260,7 +306,7 @@ int launch_grad(const unsigned char *qp, const float *v, int B, int c, const flo
     if (dv) {                                                     // sweep 1 with the second tile product
         int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
         if (rc != RTK_OK) return rc;
-        hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, 0, c, dt,
+        hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt,
                            slot, ptr, obj, (double *)nullptr, dvpos, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
                            (int32_t *)nullptr, (float *)nullptr);
         constexpr int bytes = RowsLds<KS>::TOTAL;
@@ -270,7 +316,7 @@ int launch_grad(const unsigned char *qp, const float *v, int B, int c, const flo
                            (const float *)slab, (const float *)dvpos, (const float *)bounds, dv);
     }
     if (!gO) return RTK_OK;
-    return launch_go<KS, CE_SG, CePos>(qp, v, B, c, O, N, 0, slot, ptr, obj, max_pos, dt, scale, CeGo{t0},
+    return launch_go<KS, CE_SG, CePos>(qp, v, B, c, O, N, col0, slot, ptr, obj, max_pos, dt, scale, CeGo{t0},
                                        (const unsigned char *)lw, gO, ws, L, st, fn);
 }
 
@@ -280,10 +326,34 @@ int dispatch_ce(const char *fn, int c, F f) {
     return rc != RTK_OK ? rc : rtk_check_launch(fn);
 }
 
+// The gradients on rows [col0, col0 + n_local) of the (n_ent x c) matrix, from the GLOBAL lse; the whole matrix is the
+// block (0, n_ent).
+int stream_grad(const char *fn, const void *q_packed, const float *v, int64_t batch, int c, const float *O, int64_t n_local,
+                int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                int64_t max_pos, float eps, const float *lse, const float *scale, float *dv_out, float *gO_out,
+                void *workspace, size_t ws_bytes, void *stream) {
+    RTK_REQUIRE(!gO_out || (v && scale), RTK_ERR_BAD_ARG, "%s: null operand", fn);
+    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && lse && (dv_out || gO_out), batch, c, O, n_local, col0,
+                      n_ent, max_pos, eps, workspace, ws_bytes);
+    if (rc != RTK_OK) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    if (batch == 0) return zero_go(fn, gO_out, n_local, c, st);
+    const CeWs L = layout_of(batch, c, max_pos);
+    return dispatch_ce(fn, c, [&](auto K) {
+        return launch_grad<K.value>((const unsigned char *)q_packed, v, (int)batch, c, O, (int)n_local, (int)col0, (int)n_ent,
+                                    pair_slot, pair_ptr, pair_obj, max_pos, eps, lse, scale, dv_out, gO_out,
+                                    (unsigned char *)workspace, L, st, fn);
+    });
+}
+
 }  // namespace
 
 extern "C" size_t rtk_ce_stream_workspace_bytes(int64_t batch, int64_t n_ent, int c, int64_t max_pos) {
     return stream_shape_ok(batch, n_ent, c, max_pos) ? layout_of(batch, c, max_pos).total : 0;
+}
+
+extern "C" size_t rtk_ce_stream_part_workspace_bytes(int64_t batch, int64_t n_local, int c, int64_t max_pos) {
+    return rtk_ce_stream_workspace_bytes(batch, n_local, c, max_pos);
 }
 
 extern "C" int rtk_ce_stream_rows_f32(const void *q_packed, int64_t batch, int c, const float *O, int64_t n_ent,
@@ -291,13 +361,31 @@ extern "C" int rtk_ce_stream_rows_f32(const void *q_packed, int64_t batch, int c
                                       float label_smoothing, double *loss_rows_out, float *lse_out, void *workspace,
                                       size_t ws_bytes, void *stream) {
     const char *fn = "rtk_ce_stream_rows_f32";
-    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && loss_rows_out && lse_out, batch, c, O, n_ent, 0,
-                      label_smoothing, workspace, ws_bytes);
+    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && loss_rows_out && lse_out, batch, c, O, n_ent, 0, n_ent,
+                      0, label_smoothing, workspace, ws_bytes);
     if (rc != RTK_OK || batch == 0) return rc;
     const CeWs L = layout_of(batch, c, 0);
     return dispatch_ce(fn, c, [&](auto K) {
-        return launch_fwd<K.value>((const unsigned char *)q_packed, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr, pair_obj,
-                                   label_smoothing, loss_rows_out, lse_out, (unsigned char *)workspace, L, (hipStream_t)stream);
+        return launch_fwd<K.value>((const unsigned char *)q_packed, (int)batch, c, O, (int)n_ent, 0, (int)n_ent, pair_slot,
+                                   pair_ptr, pair_obj, label_smoothing, loss_rows_out, lse_out, (float *)nullptr,
+                                   (double *)nullptr, (double *)nullptr, (unsigned char *)workspace, L, (hipStream_t)stream);
+    });
+}
+
+extern "C" int rtk_ce_stream_rows_part_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                                           int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                           const int64_t *pair_obj, float label_smoothing, float *max_out,
+                                           double *sumexp_out, double *lin_out, void *workspace, size_t ws_bytes,
+                                           void *stream) {
+    const char *fn = "rtk_ce_stream_rows_part_f32";
+    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && max_out && sumexp_out && lin_out, batch, c, O_local,
+                      n_local, col0, n_ent, 0, label_smoothing, workspace, ws_bytes);
+    if (rc != RTK_OK || batch == 0) return rc;
+    const CeWs L = layout_of(batch, c, 0);
+    return dispatch_ce(fn, c, [&](auto K) {
+        return launch_fwd<K.value>((const unsigned char *)q_packed, (int)batch, c, O_local, (int)n_local, (int)col0, (int)n_ent,
+                                   pair_slot, pair_ptr, pair_obj, label_smoothing, (double *)nullptr, (float *)nullptr, max_out,
+                                   sumexp_out, lin_out, (unsigned char *)workspace, L, (hipStream_t)stream);
     });
 }
 
@@ -306,17 +394,15 @@ extern "C" int rtk_ce_stream_grad_f32(const void *q_packed, const float *v, int6
                                       const int64_t *pair_obj, int64_t max_pos, float label_smoothing, const float *lse,
                                       const float *scale, float *dv_out, float *gO_out, void *workspace, size_t ws_bytes,
                                       void *stream) {
-    const char *fn = "rtk_ce_stream_grad_f32";
-    RTK_REQUIRE(!gO_out || (v && scale), RTK_ERR_BAD_ARG, "%s: null operand", fn);
-    int rc = check_ce(fn, q_packed && pair_slot && pair_ptr && pair_obj && lse && (dv_out || gO_out), batch, c, O, n_ent,
-                      max_pos, label_smoothing, workspace, ws_bytes);
-    if (rc != RTK_OK) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    if (batch == 0) return zero_go(fn, gO_out, n_ent, c, st);
-    const CeWs L = layout_of(batch, c, max_pos);
-    return dispatch_ce(fn, c, [&](auto K) {
-        return launch_grad<K.value>((const unsigned char *)q_packed, v, (int)batch, c, O, (int)n_ent, pair_slot, pair_ptr,
-                                    pair_obj, max_pos, label_smoothing, lse, scale, dv_out, gO_out, (unsigned char *)workspace,
-                                    L, st, fn);
-    });
+    return stream_grad("rtk_ce_stream_grad_f32", q_packed, v, batch, c, O, n_ent, 0, n_ent, pair_slot, pair_ptr, pair_obj,
+                       max_pos, label_smoothing, lse, scale, dv_out, gO_out, workspace, ws_bytes, stream);
+}
+
+extern "C" int rtk_ce_stream_grad_part_f32(const void *q_packed, const float *v, int64_t batch, int c, const float *O_local,
+                                           int64_t n_local, int64_t col0, int64_t n_ent, const int64_t *pair_slot,
+                                           const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos,
+                                           float label_smoothing, const float *lse, const float *scale, float *dv_out,
+                                           float *gO_local_out, void *workspace, size_t ws_bytes, void *stream) {
+    return stream_grad("rtk_ce_stream_grad_part_f32", q_packed, v, batch, c, O_local, n_local, col0, n_ent, pair_slot, pair_ptr,
+                       pair_obj, max_pos, label_smoothing, lse, scale, dv_out, gO_local_out, workspace, ws_bytes, stream);
 }

@@ -910,6 +910,239 @@ def ce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_s
                             float(label_smoothing))
 
 
+class _HipCeBlockLoss:
+    """The device steps of the cross-entropy block loss (``rtk_ce_stream_*_part_f32`` around stage 1 and its backward).
+    ``ShardedEntityScorer.ce_loss_1vN`` lets tests put CPU functions with these signatures in their place."""
+
+    operands = staticmethod(_HipBlockLoss.operands)
+    queries = staticmethod(_HipBlockLoss.queries)
+    stage1_backward = staticmethod(_HipBlockLoss.stage1_backward)
+
+    @staticmethod
+    def partials(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, eps):
+        """The forward sweep on the block: ``(m float32 (B,), s float64 (B,), lin float64 (B,))``."""
+        lib = _lib.load()
+        dev = O_loc.device
+        n_local, c = O_loc.shape
+        m = torch.empty(B, dtype=torch.float32, device=dev)
+        s = torch.empty(B, dtype=torch.float64, device=dev)
+        lin = torch.empty(B, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_ce_stream_part_workspace_bytes", B, n_local, c, 0))
+            _lib.check(lib.rtk_ce_stream_rows_part_f32(qp.data_ptr(), B, c, O_loc.data_ptr(), n_local, col0, n_ent,
+                                                       pair_slot.data_ptr(), pair_ptr.data_ptr(), pair_obj.data_ptr(), eps,
+                                                       m.data_ptr(), s.data_ptr(), lin.data_ptr(), ws.data_ptr(), ws.numel(),
+                                                       sp), "rtk_ce_stream_rows_part_f32")
+        return m, s, lin
+
+    @staticmethod
+    def grad(qp, v, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps, lse, scale, want_dv, want_gO):
+        """The two backward sweeps on the block from the GLOBAL ``lse`` (float64 (B,), cast to float32 here):
+        ``(dv float32 (B, c) or None, gO float32 (n_local, c) or None)``; dv is the block's unscaled share, gO carries
+        ``scale`` (one float on the device) = g / B."""
+        lib = _lib.load()
+        dev = O_loc.device
+        n_local, c = O_loc.shape
+        lse32 = lse.to(torch.float32).contiguous()
+        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
+        gO = torch.empty((n_local, c), dtype=torch.float32, device=dev) if want_gO else None
+        if not (want_dv or want_gO):
+            return dv, gO
+        max_pos = max_pos if want_gO else 0
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_ce_stream_part_workspace_bytes", B, n_local, c, max_pos))
+            _lib.check(lib.rtk_ce_stream_grad_part_f32(qp.data_ptr(), v.data_ptr(), B, c, O_loc.data_ptr(), n_local, col0,
+                                                       n_ent, pair_slot.data_ptr(), pair_ptr.data_ptr(),
+                                                       pair_obj.data_ptr(), max_pos, eps, lse32.data_ptr(), scale.data_ptr(),
+                                                       dv.data_ptr() if want_dv else None,
+                                                       gO.data_ptr() if want_gO else None, ws.data_ptr(), ws.numel(), sp),
+                       "rtk_ce_stream_grad_part_f32")
+            _strict_check(ws, sp)
+        return dv, gO
+
+
+def _ce_row_mass(pair_slot, pair_ptr, eps):
+    """w_d = (1 - eps) [n_d > 0] + eps in float64, n_d the STORED list length (0 for pair_slot[d] < 0)."""
+    s = pair_slot.clamp(min=0)
+    n = torch.where(pair_slot >= 0, pair_ptr[s + 1] - pair_ptr[s], torch.zeros_like(s))
+    return (n > 0).to(torch.float64) * (1.0 - eps) + eps
+
+
+def _ce_empty_partials(B, dev, mdt=torch.float32):
+    """What a block without rows contributes: m = -inf, s = 0, lin = 0."""
+    return (torch.full((B,), float("-inf"), dtype=mdt, device=dev),
+            torch.zeros(B, dtype=torch.float64, device=dev), torch.zeros(B, dtype=torch.float64, device=dev))
+
+
+class _CeLossBlock(torch.autograd.Function):
+    """``_CeLossStream`` on rows ``[col0, col0 + n_local)`` of the entity matrix (``rtk_ce_stream_*_part_f32``).  The
+    row's log-sum-exp couples the blocks, so the forward gives the block's ``(m, s, lin)`` and one of three things
+    completes it: the two collectives (MAX of m, SUM of ``[s exp(m - M), lin]``), a given global ``lse`` (the block's
+    share, no collectives) or nothing (the block is the whole range).  The backward is ``grad_part`` with the global
+    lse; with ``all_reduce`` dv is summed over the ranks before the (linear) stage-1 backward.  The gradient of
+    ``O_loc`` is always local.  What is saved is of size B x c and B."""
+
+    @staticmethod
+    def forward(ctx, core, R, S, O_loc, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, max_pos, col0, n_ent,
+                all_reduce, all_reduce_max, lse, steps, who="ce_loss_block_1vN"):
+        core, R, S, O_loc, h, r = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who)
+        B, (n_local, c), dev = h.numel(), O_loc.shape, core.device
+        # float32 like _CeLossStream; float64 stand-ins of the steps (tests on the CPU) keep their precision
+        ctx.ldt = ldt = torch.float64 if core.dtype == torch.float64 else torch.float32
+        ctx.eps, ctx.max_pos, ctx.B = float(eps), int(max_pos), B
+        ctx.col0, ctx.n_ent, ctx.all_reduce, ctx.steps = col0, n_ent, all_reduce, steps
+        if B == 0:
+            ctx.save_for_backward(core, R, S, O_loc)
+            return torch.zeros((), dtype=ldt, device=dev)
+        v = qp = None
+        if n_local > 0:
+            v, qp = steps.queries(core, R, S, h, r)
+            m, s, lin = steps.partials(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, ctx.eps)
+        else:                                    # a rank without rows adds nothing and still takes part in the exchanges
+            m, s, lin = _ce_empty_partials(B, dev, ldt)
+        # (the kernels form w, t0 and 1 - eps from the float32 eps they are given)
+        w = _ce_row_mass(pair_slot, pair_ptr, ctx.eps if ldt == torch.float64 else torch.tensor(ctx.eps, dtype=ldt).item())
+        if all_reduce is not None:              # MAX of B floats, then SUM of (2, B) doubles
+            M = m.clone()
+            all_reduce_max(M)
+            M = M.to(torch.float64)
+            t = torch.stack([s * torch.exp(m.to(torch.float64) - M), lin])
+            all_reduce(t)
+            lse = M + torch.log(t[0])
+            rows = w * lse + t[1]
+        elif lse is not None:                    # the block's share: its softmax mass of w lse, and its linear part
+            sigma = s * torch.exp(m.to(torch.float64) - lse)
+            rows = w * lse * sigma + lin
+        else:                                    # the whole range
+            lse = m.to(torch.float64) + torch.log(s)
+            rows = w * lse + lin
+        ctx.save_for_backward(core, R, S, O_loc, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj)
+        return (rows.sum() / B).to(ldt)
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        needs = ctx.needs_input_grad
+        if ctx.B == 0:
+            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 14
+        core, R, S, O_loc, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
+        steps, B, dev = ctx.steps, ctx.B, core.device
+        n_local, c = O_loc.shape
+        g = (grad_loss.to(device=dev, dtype=ctx.ldt).reshape(1) * (1.0 / B)).contiguous()
+        want_dv = any(needs[:3])
+        gcore = gR = gS = None
+        if n_local > 0:
+            dv, gO = steps.grad(qp, v, B, O_loc, ctx.col0, ctx.n_ent, pair_slot, pair_ptr, pair_obj, ctx.max_pos, ctx.eps,
+                                lse, g, want_dv, bool(needs[3]))
+        else:
+            dv = torch.zeros((B, c), dtype=ctx.ldt, device=dev) if want_dv else None
+            gO = torch.zeros_like(O_loc) if needs[3] else None
+        if want_dv:
+            if ctx.all_reduce is not None:       # dv, (B, c), never gS, (n_ent, b)
+                ctx.all_reduce(dv)
+            gcore, gR, gS = steps.stage1_backward(core, R, S, h, r, dv * g, needs)
+        return (gcore, gR, gS, gO) + (None,) * 14
+
+
+def _ce_slots(flt, item_ids, dev, max_pos):
+    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
+    if max_pos is None:
+        mx = getattr(flt, "max_list", None)
+        max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+    return slot, int(max_pos)
+
+
+def _ce_block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing,
+                   max_pos, all_reduce, all_reduce_max, lse, who="ce_loss_block_1vN"):
+    col0, n_ent, n_local = int(col0), int(n_ent), int(O_loc.shape[0])
+    if (all_reduce is None) != (all_reduce_max is None):
+        raise ValueError(f"{who}: all_reduce (SUM) and all_reduce_max (MAX) come together: the forward needs both")
+    if lse is not None and all_reduce is not None:
+        raise ValueError(f"{who}: lse= (the block's share, no exchange) and the collectives exclude each other")
+    B = int(subject_idx.numel())
+    if lse is not None:
+        if not isinstance(lse, torch.Tensor) or lse.dtype != torch.float64 or tuple(lse.shape) != (B,):
+            raise ValueError(f"{who}: lse must be the global log-sum-exp as a float64 tensor of shape ({B},)")
+        lse = lse.detach().to(core.device).contiguous()
+    elif all_reduce is None and not (col0 == 0 and n_local == n_ent):
+        raise ValueError(f"{who}: block [{col0}, {col0} + {n_local}) of n_ent = {n_ent} without collectives or lse=: the "
+                         "block's own log-sum-exp is not the loss")
+    slot, max_pos = _ce_slots(flt, item_ids, core.device, max_pos)
+    return _CeLossBlock.apply(core, R, S, O_loc, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
+                              float(label_smoothing), max_pos, col0, n_ent, all_reduce, all_reduce_max, lse, steps, who)
+
+
+def ce_partials_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0):
+    """The forward of ``ce_loss_1vN(matrix_free=True)`` on one block of entity rows, stopped before the logarithm
+    (stage 1 + ``rtk_ce_stream_rows_part_f32``; runs without grad): per query d and over the block's rows
+    ``[col0, col0 + n_local)`` only, ``m`` (float32) the largest logit, ``s`` (float64) ``sum_j exp(z_j - m)`` and
+    ``lin`` (float64) ``-eps / n_ent sum_j z_j - (1 - eps) / n_d sum_{t in P_d, t in block} z_t`` with the GLOBAL entity
+    count and list length.  ``ce_merge_lse`` turns the blocks' ``(m, s)`` into the global lse; the loss rows are
+    ``w_d lse_d + sum_k lin_k``.  A block without rows gives ``m = -inf, s = 0, lin = 0``."""
+    _require_gpu("core", core)
+    with torch.no_grad():
+        who = "ce_partials_block_1vN"
+        core, R, S, O_loc, h, r = _HipBlockLoss.operands(core, R, S, O_loc, subject_idx, relation_idx, int(col0), int(n_ent),
+                                                         who)
+        B = h.numel()
+        if B == 0 or O_loc.shape[0] == 0:
+            return _ce_empty_partials(B, core.device)
+        slot, _ = _ce_slots(flt, item_ids, core.device, 0)
+        _, qp = _HipBlockLoss.queries(core, R, S, h, r)
+        return _HipCeBlockLoss.partials(qp, B, O_loc, int(col0), int(n_ent), slot, flt.pair_ptr, flt.pair_obj,
+                                        float(label_smoothing))
+
+
+def ce_merge_lse(ms, ss):
+    """The global log-sum-exp, float64 (B,), from the blocks' maxima ``ms`` and sums of exponentials ``ss`` (lists of
+    ``ce_partials_block_1vN``'s ``m`` and ``s`` over a partition of the entities): ``M = max_k m_k``,
+    ``lse = M + log sum_k s_k exp(m_k - M)``, all in float64.  A block without rows has ``m = -inf, s = 0``."""
+    if len(ms) == 0 or len(ms) != len(ss):
+        raise ValueError("ce_merge_lse: one m and one s per block, at least one block")
+    m = torch.stack([t.to(torch.float64) for t in ms])
+    s = torch.stack([t.to(torch.float64) for t in ss])
+    M = m.max(dim=0).values
+    return M + torch.log((s * torch.exp(m - M)).sum(dim=0))
+
+
+def ce_loss_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0,
+                      max_pos=None, all_reduce=None, all_reduce_max=None, lse=None):
+    """``ce_loss_1vN(..., matrix_free=True)`` on one block of entity rows (an entity shard), without anything of size
+    B x n_local (``rtk_ce_stream_rows_part_f32`` / ``rtk_ce_stream_grad_part_f32``).  ``O_loc``: rows
+    ``[col0, col0 + n_local)`` of the (n_ent, c) entity matrix; ``flt`` holds GLOBAL entity ids; the smoothing term is
+    ``eps / n_ent`` and ``n_d`` the whole list's length.  S is only indexed by ``subject_idx`` and need not have n_ent
+    rows.  Unlike the BCE loss this one is not a sum over entities: the row's log-sum-exp couples the blocks, so a
+    block on its own gives ``(m, s, lin)`` (see ``ce_partials_block_1vN``) and needs one of the following.
+
+    ``all_reduce=fn, all_reduce_max=fn`` (each sums / maxes its tensor in place over the ranks; both or neither): the
+    forward exchanges B floats (MAX of ``m``, giving M) and one (2, B) float64 tensor (SUM of ``[s exp(m - M), lin]``),
+    then ``lse = M + log S``, ``rows = w lse + lin``, ``loss = rows.sum() / B``: complete and equal on every rank.  The
+    backward is ``grad_part`` with that lse; it sums dv (B x c floats) over the ranks before the stage-1 backward, so
+    core / R / S receive their complete gradients, identical on every rank -- do not average them again;
+    ``O_loc.grad`` is local.  A block without rows contributes ``m = -inf, s = 0, lin = 0``, zero dv and an empty gO
+    and still calls both functions.
+
+    ``lse=`` (float64 (B,), the GLOBAL log-sum-exp, e.g. ``ce_merge_lse`` of every block's ``ce_partials_block_1vN``;
+    anything else raises): no exchange.  This is how ONE GPU emulates P ranks, block after block.  The result is the
+    block's SHARE ``(1 / B) sum_d (w_d lse_d sigma_d + lin_d)`` with ``sigma_d = s_d exp(m_d - lse_d)`` the block's
+    softmax mass; over a partition of [0, n_ent) the sigmas sum to 1 and the shares to the loss.  Its backward is
+    ``grad_part`` with this lse (cast to float32 only at the kernel call): the block's share of the gradients of core,
+    R and S, and the gradient of ``O_loc`` -- summed / concatenated over the partition, the gradients of the loss.
+    (``lse`` is data here, not a function of the block: the share is differentiated as part of the whole loss.)
+
+    Neither: only for the whole range (``col0 == 0``, ``n_local == n_ent``); a proper block raises ``ValueError``,
+    because its own log-sum-exp is not the loss.  ``lse`` with a collective, or one collective without the other,
+    raises ``ValueError`` too.
+
+    float32, ``c <= 208``, ``c % 4 == 0`` (anything else raises; no fallback); ``max_pos`` and the ``index_check``
+    policy as ``ce_loss_1vN(matrix_free=True)``; ``max_pos`` bounds the CSR entries of the batch's queries in all
+    blocks.  Under ``no_grad`` only the forward sweep runs.  ``B == 0``: a zero loss and zero gradients."""
+    # (the mode is checked first: a wrong combination is named before anything touches a device)
+    return _ce_block_loss(_HipCeBlockLoss, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids,
+                          label_smoothing, max_pos, all_reduce, all_reduce_max, lse)
+
+
 def score_1vN(core, R, S, O, subject_idx, relation_idx, sigmoid=True, exact=False, sigmoid_mode=None,
               out_dtype=torch.float32, tables=None):
     """``sigmoid((G x_0 R[r] x_1 S[h]) . O^T)`` for a batch of (h, r) queries -> ``(B, N)``.

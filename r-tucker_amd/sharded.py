@@ -370,6 +370,58 @@ class ShardedEntityScorer:
         return ops._block_loss(steps, core, R, S, O_loc[:n_valid], lo, n_ent, subject_idx, relation_idx, flt, item_ids,
                                label_smoothing, sigmoid_mode, max_pos, reduce)
 
+    def ce_loss_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, max_pos=None,
+                    partials_fn=None, grad_fn=None, stage1_bwd_fn=None):
+        """The 1-vs-all softmax cross-entropy training loss with the entity matrix row-sharded and nothing of size
+        B x n_loc allocated (``ops.ce_loss_block_1vN`` on this rank's REAL rows, ``col0 = rank * n_loc``; ``flt`` holds
+        global entity ids).  The row's log-sum-exp couples the shards, so the forward has two exchanges: one
+        all-reduce(MAX) of the B float32 block maxima, then one all-reduce(SUM) of a (2, B) float64 tensor (the blocks'
+        sums of exponentials at the common maximum, and their linear parts); the loss is complete and equal on every
+        rank.  The backward runs on the global lse and completes dv (B x c floats) with one all-reduce(SUM) before the
+        stage-1 backward, so ``core.grad``, ``R.grad`` and ``S.grad`` are complete and identical on every rank (do not
+        average them again); ``O_loc.grad`` is this rank's rows of the gradient of O and needs no exchange.  The last
+        shard's zero padding rows are not entities: they enter neither the log-sum-exp nor the smoothing term and
+        their gradient is 0.  A rank without rows contributes ``m = -inf, s = 0, lin = 0`` and zero dv and still takes
+        part in all three exchanges.  Without a process group (world size 1) this is
+        ``ops.ce_loss_1vN(..., matrix_free=True)`` bit for bit.
+
+        Stage 1 and its backward stay replicated, as in ``bce_loss_1vN``.
+
+        ``partials_fn`` / ``grad_fn`` / ``stage1_bwd_fn`` take the arguments of ``ops._HipCeBlockLoss.partials`` /
+        ``grad`` / ``stage1_backward``; tests inject CPU functions (with ``query_vectors_fn`` / ``pack_fn`` for
+        stage 1)."""
+        from . import ops
+        n_ent, n_loc = self.shards.n_ent, self.shards.n_loc
+        lo = min(self.rank * n_loc, n_ent)
+        n_valid = max(0, min(n_loc, n_ent - lo))                 # the last shard's padding rows are not entities
+        steps = ops._HipCeBlockLoss
+        injected = partials_fn or grad_fn or stage1_bwd_fn or self.query_vectors_fn is not None
+        if injected:
+            from types import SimpleNamespace
+
+            def queries(core_, R_, S_, h, r):
+                v = self.query_vectors_fn(core_, R_, S_, h, r)
+                return v, (self.pack_fn or ops.pack_query_vectors)(v, O_loc.dtype)
+
+            steps = SimpleNamespace(
+                operands=lambda c_, R_, S_, O_, h, r, col0, n, who: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
+                queries=queries if self.query_vectors_fn is not None else steps.queries,
+                partials=partials_fn or steps.partials, grad=grad_fn or steps.grad,
+                stage1_backward=stage1_bwd_fn or steps.stage1_backward)
+        if self.world == 1 and not injected:
+            return ops.ce_loss_1vN(core, R, S, O_loc[:n_valid], subject_idx, relation_idx, flt, item_ids,
+                                   label_smoothing, matrix_free=True, max_pos=max_pos)
+        reduce_sum = reduce_max = None
+        if self.world > 1:
+            def reduce_sum(t):
+                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+
+            def reduce_max(t):
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+        return ops._ce_block_loss(steps, core, R, S, O_loc[:n_valid], lo, n_ent, subject_idx, relation_idx, flt, item_ids,
+                                  label_smoothing, max_pos, reduce_sum, reduce_max, None,
+                                  who="ShardedEntityScorer.ce_loss_1vN")
+
     # ---- top-k without the gather ----------------------------------------------------------
     def topk(self, core, R, S, O_loc, subject_idx, relation_idx, k, flt=None, slots=None, keep_idx=None,
              local_topk_fn=None, merge_fn=None, matrix_free=False, **kw):

@@ -12,8 +12,13 @@
   step  forward + backward of bce_loss_block_1vN on the block against bce_loss_1vN(matrix_free=True) on the whole
         1 M-entity matrix, with the peak of torch.cuda.max_memory_allocated over the live bytes.
 
+  --loss ce   the softmax cross-entropy loss instead (the step part only): forward + backward of
+        ce_loss_block_1vN(..., lse=) on the block -- what one rank of 8 computes, the three exchanges left out; the
+        global lse comes once, untimed, from ce_partials_block_1vN on all eight blocks and ce_merge_lse -- against
+        ce_loss_1vN(matrix_free=True) on the whole 1 M-entity matrix, alternated, with the peaks.
+
 Kernel medians: `rocprofv3 --kernel-trace --stats -- python tools/loss_shard_timing.py --part abi`.
-  --part abi | step | both    --iters N    --rounds N    --yardstick-lib PATH"""
+  --part abi | step | both    --loss bce | ce    --iters N    --rounds N    --yardstick-lib PATH"""
 import argparse
 import ctypes as C
 import os
@@ -109,34 +114,47 @@ def run_abi(params, flt, ids, iters, rounds, warm, yard_path):
     assert int(ws[:4].view(torch.int32).item()) == 0
 
 
-def run_step(params, flt, ids, iters, rounds, warm):
+def run_step(params, flt, ids, iters, rounds, warm, loss_name="bce"):
     core, R, S, O = [p.requires_grad_(True) for p in params]
     n_loc = N_ENT // P_RANKS
     col0 = BLOCK * n_loc
     O_blk = O.detach()[col0:col0 + n_loc].clone().requires_grad_(True)
     f = flt.features[ids]
     h, r = f[:, 0].contiguous(), f[:, 1].contiguous()
+    ce = loss_name == "ce"
+    lse = None
+    if ce:                                                        # the global lse, once and untimed
+        Od = O.detach()
+        parts = [rt.ce_partials_block_1vN(core, R, S, Od[k * n_loc:(k + 1) * n_loc], k * n_loc, N_ENT, h, r, flt, ids,
+                                          label_smoothing=EPS) for k in range(P_RANKS)]
+        lse = rt.ce_merge_lse([p[0] for p in parts], [p[1] for p in parts])
 
     def step_whole():
         for p in (core, R, S, O):
             p.grad = None
-        loss = rt.bce_loss_1vN(core, R, S, O, h, r, flt, ids, label_smoothing=EPS, matrix_free=True)
+        whole = rt.ce_loss_1vN if ce else rt.bce_loss_1vN
+        loss = whole(core, R, S, O, h, r, flt, ids, label_smoothing=EPS, matrix_free=True)
         loss.backward()
         return loss
 
     def step_block():
         for p in (core, R, S, O_blk):
             p.grad = None
-        loss = rt.bce_loss_block_1vN(core, R, S, O_blk, col0, N_ENT, h, r, flt, ids, label_smoothing=EPS)
+        if ce:
+            loss = rt.ce_loss_block_1vN(core, R, S, O_blk, col0, N_ENT, h, r, flt, ids, label_smoothing=EPS, lse=lse)
+        else:
+            loss = rt.bce_loss_block_1vN(core, R, S, O_blk, col0, N_ENT, h, r, flt, ids, label_smoothing=EPS)
         loss.backward()
         return loss
 
-    print(f"== step: forward + backward, B {B}, rank {RANK}; whole matrix N {N_ENT} against one block of {n_loc} rows")
+    block_name = f"one block of 8, {loss_name}_loss_block_1vN"
+    print(f"== step ({loss_name}): forward + backward, B {B}, rank {RANK}; whole matrix N {N_ENT} against one block of "
+          f"{n_loc} rows")
     res = {}
     for _ in range(rounds):
-        for name, fn in (("whole matrix, matrix_free=True", step_whole), ("one block of 8, bce_loss_block_1vN", step_block)):
+        for name, fn in (("whole matrix, matrix_free=True", step_whole), (block_name, step_block)):
             res.setdefault(name, []).append(timed(fn, warm, iters))
-    peaks = {"whole matrix, matrix_free=True": peak_of(step_whole), "one block of 8, bce_loss_block_1vN": peak_of(step_block)}
+    peaks = {"whole matrix, matrix_free=True": peak_of(step_whole), block_name: peak_of(step_block)}
     for name, ts in res.items():
         print(f"  {name:36}: " + "  ".join(f"{t:8.3f}" for t in ts) + f"  ms; peak over the live bytes {peaks[name]:8.1f} MB")
     a, b = (float(np.median(res[k])) for k in res)
@@ -147,6 +165,7 @@ def run_step(params, flt, ids, iters, rounds, warm):
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--part", default="both", choices=("abi", "step", "both"))
+    ap.add_argument("--loss", default="bce", choices=("bce", "ce"))
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=2)
@@ -156,7 +175,9 @@ if __name__ == "__main__":
     flt = rt.DeviceFilter(SyntheticPairs(N_ENT, N_REL, B, 1), "cuda")
     ids = torch.arange(B).cuda()
     params = [torch.from_numpy(x).cuda() for x in gen.make_params(N_ENT, N_REL, RANK, 322)]
-    if a.part in ("abi", "both"):
+    if a.loss == "ce" and a.part == "abi":
+        ap.error("--loss ce measures the step part only")
+    if a.part in ("abi", "both") and a.loss == "bce":
         run_abi(params, flt, ids, a.iters, a.rounds, a.warmup, a.yardstick_lib)
     if a.part in ("step", "both"):
-        run_step(params, flt, ids, a.iters, a.rounds, a.warmup)
+        run_step(params, flt, ids, a.iters, a.rounds, a.warmup, a.loss)
