@@ -60,11 +60,27 @@ typedef enum rtk_dtype {
  * bits relative to the ROW MAXIMUM); v.o ~= vh.oh + vh.ol + vl.oh, accumulated in fp32 (the vl.ol
  * term, 2^-22 relative, is dropped).  The guarantee is therefore NORMWISE PER ROW, not element-wise:
  *     |dz[d,j]|  <~  2^-21 * K * max|v_d| * max|O_j|
- * -- elements much smaller than their row's maximum lose RELATIVE precision: an element keeps all ~22
- * bits down to 2^-17 of the row maximum, then one bit less per factor of two (fp16 subnormals) to 11
- * bits at 2^-28, and is dropped entirely below 2^-39 of the row maximum -- which
+ * (typical; the worst case of the split alone is (2^-19 + 2^-22) * K * max|v_d| * max|O_j|: per k, lo is rounded to
+ * within 2^-11 ulp_fp16(hi) <= 2^-7 of the scaled element, against a factor below 2^15, on either side, plus the
+ * dropped |vl| |ol| <= 2^6, over max * max >= 2^28; tests/test_split_cases_host.py)
+ * -- elements much smaller than their row's maximum lose RELATIVE precision: an element keeps all 22
+ * bits while its scaled value is at least 2^-2 (2^-16 of a row maximum of exactly 2^14, 2^-17 of one just below
+ * 2^15), then one bit less per factor of two (lo becomes an fp16 subnormal, then zero) to 11
+ * bits at 2^-28, and is dropped entirely below 2^-39 of the row maximum (hi a subnormal, then zero) -- which
  * does not matter for a dot product dominated by the large elements but is not what an exact fp32
- * product gives for rows of extreme dynamic range.  Measured: the same error against float64 as the
+ * product gives for rows of extreme dynamic range.  The matrix core takes fp16 subnormal operands at their value (no
+ * flush): on operands whose partial sums cannot round, all three kernels return (vh.oh + vh.ol + vl.oh) 2^-(sh_v + sh_o)
+ * of the numpy model in tests/golden/split_cases.py bit for bit, subnormal lo planes included
+ * (tests/test_gpu_split_exact.py).
+ * Range: the shift is 14 - floor(log2 max), clamped to +-100 (rtk_pack_shift), so a row keeps this precision for
+ * 2^-86 <= max < 2^115.  Below 2^-86 the row is scaled by 2^100 only and its elements lose bits as small elements
+ * do (all of them below 2^-125); from about 2^116 on (max * 2^-100 > 65504) hi overflows fp16 and the scores of that
+ * row or column are not finite.  An all-zero row, or one whose maximum is not finite, gets the shift 0.  The two row
+ * factors are powers of two and the unscale multiplies them exactly as long as z itself is a normal fp32 number and
+ * sh_v + sh_o <= 149: the ws kernel forms 2^-sh_v * 2^-sh_o first, which is zero beyond that (max|v_d| * max|O_j|
+ * below about 2^-121), where v3 and cg, which multiply one factor after the other, still return a value.  Checked
+ * bit for bit with row maxima from 2^-60 to 2^60 on both sides, wherever z's unit is a normal number.
+ * Measured: the same error against float64 as the
  * reference's CPU sgemm at rank (10,200,200) (3-5e-6 relative; tests/test_gpu_parity.py,
  * test_wide_dynamic_range_rows).  RTK_SCORE_EXACT_F32 selects v_mfma_f32_32x32x2_f32 (bitwise an
  * fmaf chain) at 1/5 of the throughput when element-wise fp32 behaviour is required.
