@@ -453,6 +453,37 @@ int rtk_filtered_rank_partial_f32(const float *P, int64_t batch, int64_t n_local
                                   int32_t *counts_out, double *bce_rows_out, void *stream);
 
 /*
+ * The two counts every tie-aware rank derives from, on a block of columns of the score matrix: the twin of
+ * rtk_filtered_rank_partial_f32, with its arguments and argument checks.  For query d with object t = obj_idx[d] and
+ * p' = the row with the query's other CSR objects set to 0 (the queried object is never counted, even when it is
+ * listed; entries outside the block are skipped; the CSR lists each object once), over the block's columns
+ * j = col0 + column:
+ *   greater_out[d] = #{ j != t : p'_j >  target_scores[d] }
+ *   equal_out[d]   = #{ j != t : p'_j == target_scores[d] }
+ * both int32, IEEE comparisons: -0 == +0, a NaN never counts, a NaN target score gives 0 and 0.  The counts of the
+ * blocks of any partition add up exactly (all-reduce SUM); the whole matrix is the block col0 = 0 with
+ * rtk_target_scores_f32's scores.  The stable rank of rtk_filtered_rank_f32 is
+ * 1 + greater + #{ j < t : p'_j == p_t }, so 1 + greater <= rank <= 1 + greater + equal, and
+ *   optimistic = 1 + greater,   realistic = 1 + greater + equal / 2,   pessimistic = 1 + greater + equal.
+ */
+int rtk_filtered_tie_counts_partial_f32(const float *P, int64_t batch, int64_t n_local, int64_t ld, int64_t col0,
+                                        const float *target_scores, const int64_t *obj_idx,
+                                        const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                                        int32_t *greater_out, int32_t *equal_out, void *stream);
+
+/*
+ * Batch sums of the metrics of the three tie-aware rank types, ADDED to acc13 (the running totals of an evaluation,
+ * as rtk_rank_metrics_f64 keeps them for the stable rank):
+ *   acc13[0..3]   optimistic  (sum 1/rank, hits@1, hits@3, hits@10),  rank = 1 + greater
+ *   acc13[4..7]   realistic,                                          rank = 1 + greater + equal / 2
+ *   acc13[8..11]  pessimistic,                                        rank = 1 + greater + equal
+ *   acc13[12]     #(equal > 0): the queries whose rank the tie rule decides
+ * One workgroup, a fixed order of additions (repeated calls give the same bits).  Null pointers and batch < 1 give
+ * RTK_ERR_BAD_ARG.
+ */
+int rtk_tie_metrics_f64(const int32_t *greater, const int32_t *equal, int64_t batch, double *acc13, void *stream);
+
+/*
  * Filtered top-k link prediction: the k best objects of every (subject, relation, ?) row, leaving out the objects
  * already known to be true -- what torch.topk on the score matrix cannot do (no exclusion list, no stable tie rule).
  *   P          (batch x ld) scores, f32 or bf16 (bf16 values compare as bf16); read, never written
@@ -648,6 +679,39 @@ int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, int c, const
                                const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
                                unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
                                size_t ws_bytes, void *stream);
+
+/*
+ * The tie counts of rtk_filtered_tie_counts_partial_f32 on one block of entity rows without the (batch x n_local)
+ * score block (rtk_score_rank.hip): step 2 of the block form above with the two counts in place of their stable
+ * combination.  Arguments as rtk_score_rank_counts_*, pt the completed target scores of rtk_score_rank_targets_*:
+ *   greater_out[d] = #{ j != t : p'_j >  pt[d] },   equal_out[d] = #{ j != t : p'_j == pt[d] },   j = col0 + row,
+ * int32, with the filter rule of rtk_score_rank_counts_* (the query's other CSR objects count as probability 0, the
+ * queried object is never counted, CSR entries outside the block are ignored) and IEEE comparisons (a NaN never
+ * counts; a NaN pt gives 0 and 0).  Every probability has the bits it has in rtk_score_rank_counts_*, so over any
+ * partition of [0, n_ent) into blocks the counts add up exactly to the whole range's, and
+ * 1 + greater <= the rank of rtk_score_rank_* <= 1 + greater + equal.
+ * The kernels are those of the counts in their tie form: the entity-stationary sweep packs both counts of a tile step
+ * into one int (greater | equal << 16; neither passes 128 there) and unpacks them into two int32 partial planes, the
+ * filter pass corrects both (an entry that becomes a 0 joins `equal` when pt is 0), the finish pass adds partials
+ * and corrections in a fixed order; no atomics.
+ * Workspace: rtk_score_rank_ties_workspace_bytes (valid without a device; 0 outside the covered range), 256-byte
+ * aligned: the layout of rtk_score_rank_part_workspace_bytes, nothing grows with batch * n_local.  Its first word is
+ * the error word (not written here).
+ * Covered shapes, flags and refusals as rtk_score_rank_counts_*: RTK_SCORE_SIGMOID required; _f32 c <= 208,
+ * c % 4 == 0, 16-byte-aligned O; _bf16 c <= 512.  Everything is refused before anything is enqueued; batch == 0
+ * returns at once.
+ */
+size_t rtk_score_rank_ties_workspace_bytes(int dtype, int64_t batch, int64_t n_local, int c);
+int rtk_score_rank_tie_counts_f32(const void *q_packed, int64_t batch, int c, const float *O_local, int64_t n_local,
+                                  int64_t col0, int64_t n_ent, const float *pt, const int64_t *obj_idx,
+                                  const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                                  unsigned flags, int32_t *greater_out, int32_t *equal_out, void *workspace,
+                                  size_t ws_bytes, void *stream);
+int rtk_score_rank_tie_counts_bf16(const void *q_packed, int64_t batch, int c, const void *O_local, int64_t n_local,
+                                   int64_t col0, int64_t n_ent, const float *pt, const int64_t *obj_idx,
+                                   const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                                   unsigned flags, int32_t *greater_out, int32_t *equal_out, void *workspace,
+                                   size_t ws_bytes, void *stream);
 
 /*
  * Filtered top-k link prediction WITHOUT the (batch x n_ent) score matrix or a (batch x n_local) score block

@@ -94,6 +94,11 @@ SIGNATURES = {
     "rtk_score_rank_targets_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _u, _p, _p, _sz, _p]),
     "rtk_score_rank_counts_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
     "rtk_score_rank_counts_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
+    "rtk_filtered_tie_counts_partial_f32": (_i, [_p, _i64, _i64, _i64, _i64, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "rtk_score_rank_ties_workspace_bytes": (_sz, [_i, _i64, _i64, _i]),
+    "rtk_score_rank_tie_counts_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
+    "rtk_score_rank_tie_counts_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _p, _u, _p, _p, _p, _sz, _p]),
+    "rtk_tie_metrics_f64": (_i, [_p, _p, _i64, _p, _p]),
     "rtk_score_topk_workspace_bytes": (_sz, [_i, _i64, _i64, _i, _i]),
     "rtk_score_topk_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i, _u, _p, _p, _p, _sz, _p]),
     "rtk_score_topk_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _p, _i, _u, _p, _p, _p, _sz, _p]),

@@ -22,12 +22,15 @@ namespace {
 // (BCE logs: rtk_clog, rtk_common.h -- v_log_f32, clamped at -100 like torch's BCE, subnormal-safe)
 
 // PARTIAL: target scores come from pt_in, the "+1" is left to the caller, ids are global
-template <bool PARTIAL>
+// TIES: the two counts of the tie-aware ranks instead of their stable combination -- ranks[d] = #{j != t : p'_j > p_t},
+// eq_out[d] = #{j != t : p'_j == p_t} (rtk_filtered_tie_counts_partial_f32)
+template <bool PARTIAL, bool TIES = false>
 __global__ __launch_bounds__(256) void filtered_rank_kernel(
     const float *__restrict__ P, int B, int N, int64_t ld, int64_t col0, const float *__restrict__ pt_in,
     const int64_t *__restrict__ obj_idx,
     const int64_t *__restrict__ pair_slot, const int64_t *__restrict__ pair_ptr,
-    const int64_t *__restrict__ pair_obj, int32_t *__restrict__ ranks, double *__restrict__ bce_rows) {
+    const int64_t *__restrict__ pair_obj, int32_t *__restrict__ ranks, double *__restrict__ bce_rows,
+    int32_t *__restrict__ eq_out) {
     __shared__ int s_gt[4], s_eq[4];
     __shared__ float s_bce[4];
     const int d = blockIdx.x, t = threadIdx.x;
@@ -48,14 +51,14 @@ __global__ __launch_bounds__(256) void filtered_rank_kernel(
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             gt += p[u] > pt;
-            eq += (p[u] == pt) & (j + 256 * u < tgt);
+            eq += (p[u] == pt) & (TIES ? j + 256 * u != tgt : j + 256 * u < tgt);
             if (want_bce) bce += rtk_clog(1.0f - p[u]);
         }
     }
     for (; j < N; j += 256) {
         const float p = row[j];
         gt += p > pt;
-        eq += (p == pt) & (j < tgt);
+        eq += (p == pt) & (TIES ? j != tgt : j < tgt);
         if (want_bce) bce += rtk_clog(1.0f - p);
     }
     // the query's other true objects count as score 0 (and, for BCE, as positives)
@@ -68,8 +71,8 @@ __global__ __launch_bounds__(256) void filtered_rank_kernel(
             if (want_bce) bce += rtk_clog(p) - rtk_clog(1.0f - p);
             if (j == tgt) continue;
             gt -= p > pt;
-            eq -= (p == pt) & (j < tgt);
-            eq += (0.0f == pt) & (j < tgt);     // now a 0: ties only with a zero target score
+            eq -= (p == pt) & (TIES || j < tgt);
+            eq += (0.0f == pt) & (TIES || j < tgt);     // now a 0: ties only with a zero target score
         }
     } else if (want_bce && t == 0 && own) {     // no filter list: the queried object is the only positive
         bce += rtk_clog(pt) - rtk_clog(1.0f - pt);
@@ -86,7 +89,10 @@ __global__ __launch_bounds__(256) void filtered_rank_kernel(
         s_bce[t >> 6] = bce;
     }
     __syncthreads();
-    if (t == 0) {
+    if (t == 0 && TIES) {
+        ranks[d] = s_gt[0] + s_gt[1] + s_gt[2] + s_gt[3];
+        eq_out[d] = s_eq[0] + s_eq[1] + s_eq[2] + s_eq[3];
+    } else if (t == 0) {
         ranks[d] = (PARTIAL ? 0 : 1) + s_gt[0] + s_gt[1] + s_gt[2] + s_gt[3] + s_eq[0] + s_eq[1] + s_eq[2] + s_eq[3];
         if (want_bce) bce_rows[d] = -((double)s_bce[0] + (double)s_bce[1] + (double)s_bce[2] + (double)s_bce[3]);
     }
@@ -127,6 +133,39 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t *__rest
     if (t < 5) acc[t] += s[0][t] + s[1][t] + s[2][t] + s[3][t];   // one workgroup, launches are stream-ordered: no atomics needed
 }
 
+// acc[4 k + 0 .. 3] += sum 1/rank, #(rank <= 1 / 3 / 10) of the optimistic (k = 0: 1 + greater), realistic
+// (k = 1: 1 + greater + equal / 2) and pessimistic (k = 2: 1 + greater + equal) ranks; acc[12] += #(equal > 0).
+// rank_metrics_kernel's reduction: one workgroup, a fixed order.
+__global__ __launch_bounds__(256) void tie_metrics_kernel(const int32_t *__restrict__ greater,
+                                                          const int32_t *__restrict__ equal, int B,
+                                                          double *__restrict__ acc) {
+    __shared__ double s[4][13];
+    const int t = threadIdx.x;
+    double v[13];
+#pragma unroll
+    for (int k = 0; k < 13; ++k) v[k] = 0.0;
+    for (int d = t; d < B; d += 256) {
+        const double g = (double)greater[d], e = (double)equal[d];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const double rk = 1.0 + g + 0.5 * k * e;
+            v[4 * k] += 1.0 / rk;
+            v[4 * k + 1] += rk <= 1.0;
+            v[4 * k + 2] += rk <= 3.0;
+            v[4 * k + 3] += rk <= 10.0;
+        }
+        v[12] += e > 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 13; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+        if ((t & 63) == 0) s[t >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (t < 13) acc[t] += s[0][t] + s[1][t] + s[2][t] + s[3][t];
+}
+
 }  // namespace
 
 extern "C" int rtk_rank_metrics_f64(const int32_t *ranks, const double *bce_rows, int64_t batch, double *acc5,
@@ -141,6 +180,13 @@ extern "C" int rtk_rank_metrics_scaled_f64(const int32_t *ranks, const double *b
     RTK_REQUIRE(ranks && acc5 && batch > 0 && batch < (1ll << 31), RTK_ERR_BAD_ARG, "rtk_rank_metrics_scaled_f64: bad argument");
     hipLaunchKernelGGL(rank_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, ranks, bce_rows, (int)batch, acc5, bce_scale);
     return rtk_check_launch("rtk_rank_metrics_scaled_f64");
+}
+
+extern "C" int rtk_tie_metrics_f64(const int32_t *greater, const int32_t *equal, int64_t batch, double *acc13,
+                                   void *stream) {
+    RTK_REQUIRE(greater && equal && acc13 && batch > 0 && batch < (1ll << 31), RTK_ERR_BAD_ARG, "rtk_tie_metrics_f64: bad argument");
+    hipLaunchKernelGGL(tie_metrics_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, greater, equal, (int)batch, acc13);
+    return rtk_check_launch("rtk_tie_metrics_f64");
 }
 
 extern "C" int rtk_target_scores_f32(const float *P, int64_t batch, int64_t n_local, int64_t ld, int64_t col0,
@@ -162,8 +208,24 @@ extern "C" int rtk_filtered_rank_partial_f32(const float *P, int64_t batch, int6
     RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "rtk_filtered_rank_partial_f32: pair_slot without the CSR arrays");
     RTK_REQUIRE(batch < (1ll << 31) && n_local < (1ll << 31), RTK_ERR_UNSUPPORTED, "rtk_filtered_rank_partial_f32: dimension too large");
     hipLaunchKernelGGL(filtered_rank_kernel<true>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, P, (int)batch,
-                       (int)n_local, ld, col0, target_scores, obj_idx, pair_slot, pair_ptr, pair_obj, counts_out, bce_rows_out);
+                       (int)n_local, ld, col0, target_scores, obj_idx, pair_slot, pair_ptr, pair_obj, counts_out, bce_rows_out,
+                       (int32_t *)nullptr);
     return rtk_check_launch("rtk_filtered_rank_partial_f32");
+}
+
+extern "C" int rtk_filtered_tie_counts_partial_f32(const float *P, int64_t batch, int64_t n_local, int64_t ld, int64_t col0,
+                                                   const float *target_scores, const int64_t *obj_idx,
+                                                   const int64_t *pair_slot, const int64_t *pair_ptr,
+                                                   const int64_t *pair_obj, int32_t *greater_out, int32_t *equal_out,
+                                                   void *stream) {
+    RTK_REQUIRE(P && obj_idx && greater_out && equal_out && target_scores, RTK_ERR_BAD_ARG, "rtk_filtered_tie_counts_partial_f32: null operand");
+    RTK_REQUIRE(batch > 0 && n_local > 0 && ld >= n_local && col0 >= 0, RTK_ERR_BAD_ARG, "rtk_filtered_tie_counts_partial_f32: bad sizes");
+    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "rtk_filtered_tie_counts_partial_f32: pair_slot without the CSR arrays");
+    RTK_REQUIRE(batch < (1ll << 31) && n_local < (1ll << 31), RTK_ERR_UNSUPPORTED, "rtk_filtered_tie_counts_partial_f32: dimension too large");
+    hipLaunchKernelGGL((filtered_rank_kernel<true, true>), dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, P,
+                       (int)batch, (int)n_local, ld, col0, target_scores, obj_idx, pair_slot, pair_ptr, pair_obj, greater_out,
+                       (double *)nullptr, equal_out);
+    return rtk_check_launch("rtk_filtered_tie_counts_partial_f32");
 }
 
 extern "C" int rtk_filtered_rank_f32(const float *P, int64_t batch, int64_t n_ent, int64_t ld,
@@ -176,6 +238,6 @@ extern "C" int rtk_filtered_rank_f32(const float *P, int64_t batch, int64_t n_en
     RTK_REQUIRE(batch < (1ll << 31) && n_ent < (1ll << 31), RTK_ERR_UNSUPPORTED, "rtk_filtered_rank_f32: dimension too large");
     hipLaunchKernelGGL(filtered_rank_kernel<false>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, P, (int)batch,
                        (int)n_ent, ld, (int64_t)0, (const float *)nullptr, obj_idx, pair_slot, pair_ptr, pair_obj, ranks_out,
-                       bce_rows_out);
+                       bce_rows_out, (int32_t *)nullptr);
     return rtk_check_launch("rtk_filtered_rank_f32");
 }

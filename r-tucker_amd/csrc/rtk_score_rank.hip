@@ -13,6 +13,12 @@
 // rtk_score_rank_* is the one-block call: both steps at col0 = 0, n_local = n_ent, pt kept in the workspace and the
 // finish pass writing 1 + count.  There is one set of kernels.
 //
+// rtk_score_rank_tie_counts_* is step 2 with the two counts of the tie-aware ranks in place of their stable combination:
+//
+//   greater = #{ j != t : p'_j > pt }      equal = #{ j != t : p'_j == pt }      (1 + greater <= rank <= 1 + greater + equal)
+//
+// from the TIES instantiations of count_kernel and filter_kernel and from finish_ties_kernel.
+//
 // Step 1 is target_kernel: one wave per query, p_t from a 32x32 MFMA tile whose rows are all query d and whose column 0
 // is O[t_d].  Step 2 is three launches on the caller's stream:
 //
@@ -91,8 +97,15 @@ struct CountLds {
 // What count_kernel does with the sweep (rtk_score_rank_kernel.h).  The 32 x 32 probabilities are compared with pt and
 // counted, never stored.  A lane holds one entity and 16 query rows: the 16 counts (and BCE terms) are summed over the
 // 32 entity lanes by the butterfly, over the 4 waves in wave order, and added to the workgroup's own row of partials.
-template <typename T, int KS, int SG, bool BCE>
+//
+// TIES: the two counts of the tie-aware ranks instead (rtk_score_rank_tie_counts_*): an element contributes p > pt and
+// (p == pt) & (j != t).  A 32-lane sum of either is at most 32 and the sum over the 4 waves at most 128, so both travel
+// as one int (greater | equal << 16) through the butterfly and the LDS slot -- the exchanges and the LDS of the plain
+// count -- and publish unpacks them into two int32 planes (totals reach n_local): greater into part_cnt, equal into
+// the plane that holds the BCE partials otherwise (the same size).
+template <typename T, int KS, int SG, bool BCE, bool TIES = false>
 struct CountSweep {
+    static_assert(!(BCE && TIES), "the tie counts come without BCE sums");
     typedef CountLds<T, KS> L;
     static constexpr int EXTRA = L::EXTRA;
     int B, col0, n_ent;
@@ -131,7 +144,8 @@ struct CountSweep {
             for (int q = 0; q < 4; ++q) {
                 const int e = 4 * g + q;
                 const float p = f.template prob<SG>(acc[e], sr4[q]);
-                const int k = (p > pt4[q]) + ((p == pt4[q]) & (jg < (int)tg4[q]));
+                const int k = TIES ? (p > pt4[q]) | (((p == pt4[q]) & (jg != (int)tg4[q])) << 16)
+                                   : (p > pt4[q]) + ((p == pt4[q]) & (jg < (int)tg4[q]));
                 cnt[e] = valid ? k : 0;
                 bce[e] = (BCE && valid) ? rtk_clog(1.0f - p) : 0.f;
             }
@@ -149,11 +163,17 @@ struct CountSweep {
     // tile order; the workgroup's first entity tile writes them
     __device__ __forceinline__ void publish(SweepLane ln, int cur, int i, int mt, int slot, int, bool first) const {
         const int wave = ln.wave, r = ln.r, h = ln.h;
-        if (wave == (i & (RP_WAVES - 1)) && (BCE || h == 0)) {
+        if (wave == (i & (RP_WAVES - 1)) && (BCE || TIES || h == 0)) {
             const int d = mt * 32 + r;
             if (d < B) {
                 const int64_t at = (int64_t)slot * B + d;
-                if (h == 0) {
+                if (TIES) {                                        // half 0: greater, half 1: equal
+                    const int *rc = reinterpret_cast<const int *>(sweep_lds + L::RED + cur * L::RED_BUF);
+                    const int both = rc[r] + rc[32 + r] + rc[64 + r] + rc[96 + r];
+                    const int s = h == 0 ? (both & 0xffff) : (both >> 16);
+                    int32_t *plane = h == 0 ? part_cnt : reinterpret_cast<int32_t *>(part_bce);
+                    plane[at] = first ? s : plane[at] + s;
+                } else if (h == 0) {
                     const int *rc = reinterpret_cast<const int *>(sweep_lds + L::RED + cur * L::RED_BUF);
                     const int s = rc[r] + rc[32 + r] + rc[64 + r] + rc[96 + r];
                     part_cnt[at] = first ? s : part_cnt[at] + s;
@@ -168,20 +188,22 @@ struct CountSweep {
 };
 
 // Step 2, dense part.  Workgroup (slot, qs): entity tiles slot, slot + n_slots, ...; query tiles of range qs.
-template <typename T, int KS, int SG, bool BCE>
+template <typename T, int KS, int SG, bool BCE, bool TIES = false>
 __global__ __launch_bounds__(64 * RP_WAVES, 2) void count_kernel(const unsigned char *__restrict__ qp, int B,
                                                                  const T *__restrict__ O, int n_local, int c, int col0,
                                                                  int n_ent, const int64_t *__restrict__ obj_idx,
                                                                  const float *__restrict__ pt_in, int n_slots, int qsplit,
                                                                  int32_t *__restrict__ part_cnt,
                                                                  float *__restrict__ part_bce, bool vec) {
-    CountSweep<T, KS, SG, BCE> pol{B, col0, n_ent, obj_idx, pt_in, part_cnt, part_bce};
+    CountSweep<T, KS, SG, BCE, TIES> pol{B, col0, n_ent, obj_idx, pt_in, part_cnt, part_bce};
     sweep<T, KS, SG>(pol, qp, B, O, n_local, c, vec, n_slots, qsplit);
 }
 
 // Step 2, the filter correction: wave u of query d scores the CSR entries [i0 + 32 (u + RP_UQ k), + 32) of the query,
 // one per column, and corrects the count for those inside the block (filtered_rank_kernel's rule, global ids).
-template <typename T, int KS, int SG>
+// TIES: the corrections of the two tie counts -- the entry leaves `greater` or `equal` and, now a 0, joins `equal` when
+// the target score is 0 -- as ints in fc_cnt (greater) and fc_bce (equal).
+template <typename T, int KS, int SG, bool TIES = false>
 __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned char *__restrict__ qp, int B,
                                                                const T *__restrict__ O, int n_local, int c, int col0,
                                                                int n_ent, const int64_t *__restrict__ obj_idx,
@@ -195,7 +217,7 @@ __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned ch
     const int w = __builtin_amdgcn_readfirstlane((int)blockIdx.x * RP_WAVES + (int)(threadIdx.x >> 6));
     const int d = w / RP_UQ, u = w % RP_UQ;
     if (d >= B) return;
-    int cnt = 0;
+    int cnt = 0, eq = 0;
     float bce = 0.f;
     const int64_t s = pair_slot[d];
     if (s >= 0) {
@@ -214,7 +236,13 @@ __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned ch
                 const float p = q.template score<SG>(f, O, ok ? (int64_t)(jr - col0) : 0, c, h, vec);
                 if (h == 0 && ok) {                                    // element 0 of lane r: row 0, column r
                     if (want_bce) bce += rtk_clog(p) - rtk_clog(1.0f - p);
-                    if (jr != tgt) {
+                    if (TIES) {
+                        if (jr != tgt) {
+                            cnt -= p > pt;
+                            eq -= p == pt;
+                            eq += 0.0f == pt;                 // now a 0: ties only with a zero target score
+                        }
+                    } else if (jr != tgt) {
                         cnt -= p > pt;
                         cnt -= (p == pt) & (jr < tgt);
                         cnt += (0.0f == pt) & (jr < tgt);     // now a 0: ties only with a zero target score
@@ -226,11 +254,12 @@ __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned ch
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) {
         cnt += __shfl_xor(cnt, o);
-        bce += __shfl_xor(bce, o);
+        if (TIES) eq += __shfl_xor(eq, o);
+        else bce += __shfl_xor(bce, o);
     }
     if (lane == 0) {
         fc_cnt[(int64_t)d * RP_UQ + u] = cnt;
-        fc_bce[(int64_t)d * RP_UQ + u] = bce;
+        fc_bce[(int64_t)d * RP_UQ + u] = TIES ? __int_as_float(eq) : bce;
     }
 }
 
@@ -281,6 +310,44 @@ __global__ __launch_bounds__(256) void finish_kernel(int B, int n_slots, int col
     }
     counts_out[d] = base + cnt;
     if (want_bce) bce_rows_out[d] = -bce;
+}
+
+// The finish pass of the tie counts: greater_out[d] / equal_out[d] = partials of the slots + the filter waves'
+// corrections, in finish_kernel's layout and order (32 queries per workgroup, 8 threads per query).
+__global__ __launch_bounds__(256) void finish_ties_kernel(int B, int n_slots, const int32_t *__restrict__ part_gt,
+                                                          const int32_t *__restrict__ part_eq,
+                                                          const int32_t *__restrict__ fc_gt,
+                                                          const int32_t *__restrict__ fc_eq,
+                                                          const int64_t *__restrict__ pair_slot,
+                                                          int32_t *__restrict__ greater_out,
+                                                          int32_t *__restrict__ equal_out) {
+    __shared__ int s_gt[8][32], s_eq[8][32];
+    const int t = threadIdx.x, q = t & 31, sl = t >> 5;
+    const int d = min((int)blockIdx.x * 32 + q, B - 1);
+    int gt = 0, eq = 0;
+    for (int k = sl; k < n_slots; k += 8) {
+        gt += part_gt[(int64_t)k * B + d];
+        eq += part_eq[(int64_t)k * B + d];
+    }
+    s_gt[sl][q] = gt;
+    s_eq[sl][q] = eq;
+    __syncthreads();
+    if (sl != 0 || (int)blockIdx.x * 32 + q >= B) return;
+    gt = eq = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        gt += s_gt[k][q];
+        eq += s_eq[k][q];
+    }
+    if (pair_slot && pair_slot[d] >= 0) {
+#pragma unroll
+        for (int u = 0; u < RP_UQ; ++u) {
+            gt += fc_gt[(int64_t)d * RP_UQ + u];
+            eq += fc_eq[(int64_t)d * RP_UQ + u];
+        }
+    }
+    greater_out[d] = gt;
+    equal_out[d] = eq;
 }
 
 struct PartLayout {
@@ -334,6 +401,33 @@ int launch_counts(const unsigned char *qp, int B, const T *O, int n_local, int c
     return RTK_OK;
 }
 
+// The tie counts on the stream: count_kernel and filter_kernel in their TIES forms on the block layout (the BCE planes
+// hold the equal counts), finish_ties_kernel.
+template <typename T, int KS, int SG>
+int launch_ties(const unsigned char *qp, int B, const T *O, int n_local, int c, int col0, int n_ent, const float *pt,
+                const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
+                int32_t *greater, int32_t *equal, unsigned char *ws, hipStream_t st, const char *fn) {
+    const PartLayout L = layout_of(B, n_local);
+    const SweepGrid g = grid_of(B, n_local, RP_SLOTS);
+    int32_t *pgt = reinterpret_cast<int32_t *>(ws + L.cnt);
+    float *peq = reinterpret_cast<float *>(ws + L.bce);
+    int32_t *fgt = reinterpret_cast<int32_t *>(ws + L.fcnt);
+    float *feq = reinterpret_cast<float *>(ws + L.fbce);
+    const bool vec = vec_rows(O, c);
+    const int rc = launch_lds<&count_kernel<T, KS, SG, false, true>, CountLds<T, KS>::TOTAL>(
+        dim3((unsigned)(g.n_slots * g.qsplit)), dim3(64 * RP_WAVES), st, fn, qp, B, O, n_local, c, col0, n_ent, obj_idx, pt,
+        g.n_slots, g.qsplit, pgt, peq, vec);
+    if (rc != RTK_OK) return rc;
+    if (pair_slot)
+        hipLaunchKernelGGL((filter_kernel<T, KS, SG, true>), dim3((unsigned)rtk_cdiv((int64_t)B * RP_UQ, RP_WAVES)),
+                           dim3(64 * RP_WAVES), 0, st, qp, B, O, n_local, c, col0, n_ent, obj_idx, pt, pair_slot, pair_ptr,
+                           pair_obj, fgt, feq, false, vec);
+    hipLaunchKernelGGL(finish_ties_kernel, dim3((unsigned)rtk_cdiv(B, 32)), dim3(256), 0, st, B, g.n_slots, pgt,
+                       reinterpret_cast<const int32_t *>(peq), fgt, reinterpret_cast<const int32_t *>(feq), pair_slot, greater,
+                       equal);
+    return RTK_OK;
+}
+
 // the checks every entry point shares; `out` is the call's output, `ws_extra` what it keeps behind the block layout
 template <typename T>
 int check_rank(const char *fn, const void *q_packed, int64_t batch, int c, const T *O, int64_t n_local, int64_t col0,
@@ -369,6 +463,23 @@ int rank_counts(const char *fn, const void *q_packed, int64_t batch, int c, cons
         return launch_counts<T, K.value, SG.value>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c, (int)col0,
                                                    (int)n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, 0, counts_out,
                                                    bce_rows_out, (unsigned char *)workspace, (hipStream_t)stream, fn);
+    });
+}
+
+template <typename T>
+int rank_tie_counts(const char *fn, const void *q_packed, int64_t batch, int c, const T *O, int64_t n_local, int64_t col0,
+                    int64_t n_ent, const float *pt, const int64_t *obj_idx, const int64_t *pair_slot,
+                    const int64_t *pair_ptr, const int64_t *pair_obj, unsigned flags, int32_t *greater_out,
+                    int32_t *equal_out, void *workspace, size_t ws_bytes, void *stream) {
+    RTK_REQUIRE(pt, RTK_ERR_BAD_ARG, "%s: null operand", fn);
+    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "%s: pair_slot without the CSR arrays", fn);
+    const int rc = check_rank<T>(fn, q_packed, batch, c, O, n_local, col0, n_ent, obj_idx, flags,
+                                  equal_out ? greater_out : nullptr, workspace, ws_bytes);
+    if (rc != RTK_OK || batch == 0) return rc;
+    return dispatch<T>(fn, c, flags, [&](auto K, auto SG) {
+        return launch_ties<T, K.value, SG.value>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c, (int)col0,
+                                                 (int)n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, greater_out,
+                                                 equal_out, (unsigned char *)workspace, (hipStream_t)stream, fn);
     });
 }
 
@@ -457,4 +568,31 @@ extern "C" int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, i
     return rank_counts<rtk_bf16>("rtk_score_rank_counts_bf16", q_packed, batch, c, (const rtk_bf16 *)O_local, n_local, col0,
                                  n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, flags, counts_out, bce_rows_out,
                                  workspace, ws_bytes, stream);
+}
+
+// the block layout (the tie counts use its BCE planes for the equal counts); 0 outside the covered range
+extern "C" size_t rtk_score_rank_ties_workspace_bytes(int dtype, int64_t batch, int64_t n_local, int c) {
+    if (batch < 0 || batch >= (1ll << 31) - 32 || n_local < 1 || n_local >= (1ll << 31) - 64 || c < 1) return 0;
+    if (dtype == RTK_F32 ? (c > 16 * SW_MAX_KS_F32 || c % 4 != 0) : (dtype != RTK_BF16 || c > 16 * SW_MAX_KS_BF16)) return 0;
+    return layout_of(batch, n_local).total;
+}
+
+extern "C" int rtk_score_rank_tie_counts_f32(const void *q_packed, int64_t batch, int c, const float *O_local,
+                                             int64_t n_local, int64_t col0, int64_t n_ent, const float *pt,
+                                             const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                             const int64_t *pair_obj, unsigned flags, int32_t *greater_out,
+                                             int32_t *equal_out, void *workspace, size_t ws_bytes, void *stream) {
+    return rank_tie_counts<float>("rtk_score_rank_tie_counts_f32", q_packed, batch, c, O_local, n_local, col0, n_ent, pt,
+                                  obj_idx, pair_slot, pair_ptr, pair_obj, flags, greater_out, equal_out, workspace, ws_bytes,
+                                  stream);
+}
+
+extern "C" int rtk_score_rank_tie_counts_bf16(const void *q_packed, int64_t batch, int c, const void *O_local,
+                                              int64_t n_local, int64_t col0, int64_t n_ent, const float *pt,
+                                              const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                              const int64_t *pair_obj, unsigned flags, int32_t *greater_out,
+                                              int32_t *equal_out, void *workspace, size_t ws_bytes, void *stream) {
+    return rank_tie_counts<rtk_bf16>("rtk_score_rank_tie_counts_bf16", q_packed, batch, c, (const rtk_bf16 *)O_local, n_local,
+                                     col0, n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, flags, greater_out, equal_out,
+                                     workspace, ws_bytes, stream);
 }

@@ -180,9 +180,10 @@ def train_one_epoch(model, optimizer, train_flt: DeviceFilter, batch_size, label
     return train_loss / denom, train_grad_norm / denom
 
 
-def evaluate(model, dataset, batch_size=512, flt: DeviceFilter = None):
-    """``train.py:94-125``: ``(metrics dict averaged over the queries, mean BCE loss)``."""
-    return _evaluate(model, dataset, batch_size=batch_size, flt=flt)
+def evaluate(model, dataset, batch_size=512, flt: DeviceFilter = None, rank_type=None):
+    """``train.py:94-125``: ``(metrics dict averaged over the queries, mean BCE loss)``.  ``rank_type``: None (the
+    stable rank) or a tie-aware rank type, as ``evaluation.evaluate``."""
+    return _evaluate(model, dataset, batch_size=batch_size, flt=flt, rank_type=rank_type)
 
 
 def train(model, optimizer, train_set, val_set, test_set, config, regulizer, scheduler=None, log=print, wandb_run=None,

@@ -8,7 +8,11 @@ the filter lists of every (subject, relation) pair are uploaded once as a CSR an
 ``rtk_filtered_rank_f32`` counts the rank of the queried object in one pass over the
 score row.  Tie order is that of a stable descending sort (torch's CUDA sort /
 ``sort(stable=True)``); the reference's default CPU sort is unstable, so on exactly tied
-scores its own ranks are implementation-defined.
+scores its own ranks are implementation-defined.  What can be said about a tied
+target on any host is the interval ``[1 + greater, 1 + greater + equal]``:
+``filtered_tie_counts`` / ``tie_counts_block`` return the two counts, and
+``evaluate(..., rank_type=...)`` the metrics of the optimistic, realistic or pessimistic rank
+with the share of tied queries.
 """
 from __future__ import annotations
 
@@ -216,6 +220,75 @@ def rank_counts_block(P: torch.Tensor, obj_idx: torch.Tensor, col0: int, target_
     return (counts, bce) if want_bce else counts
 
 
+def tie_counts_block(P: torch.Tensor, obj_idx: torch.Tensor, col0: int, target_scores: torch.Tensor,
+                     flt: DeviceFilter = None, item_ids: torch.Tensor = None):
+    """This column block's share of the two tie counts (``rtk_filtered_tie_counts_partial_f32``) ->
+    ``(greater, equal)`` int32 (B,): the columns j != t of the block with ``p'_j > p_t`` and with ``p'_j == p_t``,
+    p' = the row with the query's other known-true objects set to 0.  Arguments as ``rank_counts_block``; the blocks'
+    counts add up exactly (all-reduce SUM)."""
+    lib = _lib.load()
+    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2
+            or P.stride(1) != 1):
+        raise RuntimeError("P must be a float32 (B, n_local) GPU tensor with unit column stride")
+    B, n_loc = P.shape
+    dev = P.device
+    obj = obj_idx.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    if obj.numel() != B:
+        raise RuntimeError("obj_idx must have one entry per row of P")
+    greater = torch.empty(B, dtype=torch.int32, device=dev)
+    equal = torch.empty(B, dtype=torch.int32, device=dev)
+    slot = ptr = objs = None
+    if flt is not None:
+        slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
+        ptr, objs = flt.pair_ptr, flt.pair_obj
+    pt = target_scores.to(device=dev, dtype=torch.float32).contiguous()
+    if pt.numel() != B:
+        raise RuntimeError("target_scores must have one entry per row of P")
+    if B == 0:
+        return greater, equal
+    with torch.cuda.device(dev):
+        sp = torch.cuda.current_stream(dev).cuda_stream
+        _lib.check(lib.rtk_filtered_tie_counts_partial_f32(P.data_ptr(), B, n_loc, P.stride(0), int(col0), pt.data_ptr(),
+                                                           obj.data_ptr(),
+                                                           slot.data_ptr() if slot is not None else None,
+                                                           ptr.data_ptr() if ptr is not None else None,
+                                                           objs.data_ptr() if objs is not None else None,
+                                                           greater.data_ptr(), equal.data_ptr(), sp),
+                   "rtk_filtered_tie_counts_partial_f32")
+    return greater, equal
+
+
+def filtered_tie_counts(P: torch.Tensor, obj_idx: torch.Tensor, flt: DeviceFilter = None, item_ids: torch.Tensor = None):
+    """The tie counts ``(greater, equal)`` (int32, B) of ``obj_idx`` in the rows of ``P`` after filtering: the whole
+    matrix as the block ``col0 = 0``.  ``1 + greater <= filtered_ranks <= 1 + greater + equal``."""
+    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2
+            or P.stride(1) != 1):
+        raise RuntimeError("P must be a float32 (B, N) GPU tensor with unit column stride")
+    if P.shape[0] == 0:
+        return tie_counts_block(P, obj_idx, 0, torch.empty(0, dtype=torch.float32, device=P.device), flt, item_ids)
+    return tie_counts_block(P, obj_idx, 0, target_scores_block(P, obj_idx, 0), flt, item_ids)
+
+
+_TIE_TYPES = ("optimistic", "realistic", "pessimistic")      # the order of rtk_tie_metrics_f64's accumulators
+
+
+def _check_tie_type(rank_type):
+    if rank_type not in _TIE_TYPES:
+        raise ValueError(f"rank_type = {rank_type!r}: None (the stable rank), 'optimistic', 'realistic' or 'pessimistic'")
+
+
+def metrics_from_tie_counts(greater: torch.Tensor, equal: torch.Tensor):
+    """Batch SUMS of every tie-aware rank type from the two counts: ``{"optimistic": {"mrr", "hits@1", "hits@3",
+    "hits@10"}, "realistic": ..., "pessimistic": ..., "tied": #(equal > 0)}`` (what ``rtk_tie_metrics_f64`` adds up)."""
+    from .ops import ranks_from_tie_counts
+    out = {}
+    for name in _TIE_TYPES:
+        r = ranks_from_tie_counts(greater, equal, name)
+        out[name] = {"mrr": (1.0 / r).sum(), "hits@1": (r <= 1).sum(), "hits@3": (r <= 3).sum(), "hits@10": (r <= 10).sum()}
+    out["tied"] = (torch.as_tensor(equal) > 0).sum()
+    return out
+
+
 def metrics_from_ranks(ranks: torch.Tensor):
     """Batch SUMS like ``src/utils/metrics.py`` (mrr = sum 1/rank, hits@k = #(rank <= k))."""
     r = ranks.to(torch.float64)
@@ -239,18 +312,35 @@ class _EvalPlan:
         self.qp = torch.empty(lib.rtk_packed_query_bytes(_dtype_code(dtype == torch.bfloat16), B, c), dtype=torch.uint8,
                               device=device)
         self.ws_bytes = lib.rtk_from_tables_workspace_bytes(B, n_rel)
+        self.ties = None
+
+    def tie_buffers(self):
+        """Target scores, the two tie counts and the 13 running sums of ``evaluate(rank_type=...)`` (made on first use)."""
+        if self.ties is None:
+            B, dev = self.ranks.numel(), self.ranks.device
+            self.ties = (torch.empty(B, dtype=torch.float32, device=dev), torch.empty(B, dtype=torch.int32, device=dev),
+                         torch.empty(B, dtype=torch.int32, device=dev), torch.zeros(13, dtype=torch.float64, device=dev))
+        return self.ties
 
 
 @torch.no_grad()
-def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = None):
+def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = None, rank_type=None):
     """The reference's ``evaluate`` loop on the device.  ``dataset``: a test-mode ``KG_dataset``.
     Returns (metrics dict averaged over queries, mean BCE loss) like train.py:123-125.
+
+    ``rank_type``: None ranks by the stable rule (the metrics above).  "optimistic", "realistic" or "pessimistic"
+    return that tie-aware rank type's ``mrr / hits@1 / hits@3 / hits@10`` instead, plus ``tied``, the share of the
+    queries with a competitor at exactly the target's score -- when it is not small, the tie rule and not the model
+    decides a stable-rule MRR.  The loss is the same; the tie counts cost one more pass over each batch's scores
+    (``rtk_filtered_tie_counts_partial_f32``, ``rtk_tie_metrics_f64``).
 
     Per batch: stage 1 against the relation tables of the frozen parameters, the score kernel, the filtered-rank
     kernel over the score matrix, the metric sums -- four calls into the C ABI on buffers that are allocated once per
     (dataset, batch size) and reused; the filter CSR is built once per dataset object.  Out-of-range ids are reported
     at the pass's own synchronisation point (reference: IndexError)."""
     from . import ops
+    if rank_type is not None:
+        _check_tie_type(rank_type)
     device = torch.device(device) if device is not None else next(model.parameters()).device
     if device.type == "cuda" and device.index is None:
         device = torch.device("cuda", torch.cuda.current_device())
@@ -265,7 +355,7 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
     if (b != c or core.dtype not in (torch.float32, torch.bfloat16) or not ops._packed_stage2(c, exact=False)
             or not core.is_cuda
             or any(t.dtype != core.dtype or t.device != core.device or not t.is_contiguous() for t in (R, S, O))):
-        return _evaluate_generic(model, dataset, batch_size, device, flt)      # (raises what the closure raises)
+        return _evaluate_generic(model, dataset, batch_size, device, flt, rank_type)      # (raises what the closure raises)
     lib = _lib.load()
     N, n_rel = O.shape[0], R.shape[0]
     bf16 = core.dtype == torch.bfloat16
@@ -288,6 +378,10 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
         tp, Sp, Op, wsp, wsn = tables.data_ptr(), S.data_ptr(), O.data_ptr(), ws.data_ptr(), ws.numel()
         hp, rp, op, slp = flt.subj.data_ptr(), flt.rel.data_ptr(), flt.obj.data_ptr(), flt.slot_of_item.data_ptr()
         ptr, objs = flt.pair_ptr.data_ptr(), flt.pair_obj.data_ptr()
+        if rank_type is not None:
+            tie_pt, tie_gt, tie_eq, tie_acc = plan.tie_buffers()
+            tie_acc.zero_()
+            ptp, gtp, eqp, tap = tie_pt.data_ptr(), tie_gt.data_ptr(), tie_eq.data_ptr(), tie_acc.data_ptr()
         n_batches = 0
         for lo in range(0, n, batch_size):
             nb = min(batch_size, n - lo)
@@ -299,15 +393,31 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
                        "rtk_filtered_rank_f32")
             # the reference averages the per-batch MEAN losses (train.py:113,125)
             _lib.check(lib.rtk_rank_metrics_scaled_f64(ranks, bce, nb, 1.0 / (nb * N), acc, sp), "rtk_rank_metrics_scaled_f64")
+            if rank_type is not None:                        # one more pass over P: the whole matrix as the block col0 = 0
+                _lib.check(lib.rtk_target_scores_f32(P, nb, N, plan.ld, 0, op + o8, ptp, sp), "rtk_target_scores_f32")
+                _lib.check(lib.rtk_filtered_tie_counts_partial_f32(P, nb, N, plan.ld, 0, ptp, op + o8, slp + o8, ptr, objs,
+                                                                   gtp, eqp, sp), "rtk_filtered_tie_counts_partial_f32")
+                _lib.check(lib.rtk_tie_metrics_f64(gtp, eqp, nb, tap, sp), "rtk_tie_metrics_f64")
             n_batches += 1
     acc = plan.acc.cpu().tolist()
+    tie_sums = tie_acc.cpu().tolist() if rank_type is not None else None
     ops.check_device_errors(device)
+    if rank_type is not None:
+        return _tie_metrics(tie_sums, rank_type, n), acc[4] / max(n_batches, 1)
     sums = {"mrr": acc[0] / n, "hits@1": acc[1] / n, "hits@3": acc[2] / n, "hits@10": acc[3] / n}
     return sums, acc[4] / max(n_batches, 1)
 
 
+def _tie_metrics(acc13, rank_type, n):
+    """The metrics dictionary of one rank type from rtk_tie_metrics_f64's 13 running sums over ``n`` queries."""
+    k = 4 * _TIE_TYPES.index(rank_type)
+    n = max(n, 1)
+    return {"mrr": acc13[k] / n, "hits@1": acc13[k + 1] / n, "hits@3": acc13[k + 2] / n, "hits@10": acc13[k + 3] / n,
+            "tied": acc13[12] / n}
+
+
 @torch.no_grad()
-def _evaluate_generic(model, dataset, batch_size, device, flt):
+def _evaluate_generic(model, dataset, batch_size, device, flt, rank_type=None):
     """The same loop through the model's closure (any operand the closure accepts; shapes the fast path does not
     cover end in the closure's own error)."""
     from .ops import check_device_errors, index_check
@@ -318,6 +428,7 @@ def _evaluate_generic(model, dataset, batch_size, device, flt):
     n = len(dataset)
     lib = _lib.load()
     acc = torch.zeros(5, dtype=torch.float64, device=device)   # running sums on the device: one sync at the end
+    tie_acc = torch.zeros(13, dtype=torch.float64, device=device) if rank_type is not None else None
     loss_terms = 0
     n_batches = 0
     # out-of-range ids: checked once, at the loop's own synchronisation point below (reference: IndexError)
@@ -333,8 +444,15 @@ def _evaluate_generic(model, dataset, batch_size, device, flt):
             with torch.cuda.device(device):
                 _lib.check(lib.rtk_rank_metrics_f64(ranks.data_ptr(), bce.data_ptr(), hi - lo, acc.data_ptr(),
                                                     torch.cuda.current_stream(device).cuda_stream), "rtk_rank_metrics_f64")
+                if rank_type is not None:
+                    greater, equal = filtered_tie_counts(P, f[:, 2], flt, ids)
+                    _lib.check(lib.rtk_tie_metrics_f64(greater.data_ptr(), equal.data_ptr(), hi - lo, tie_acc.data_ptr(),
+                                                       torch.cuda.current_stream(device).cuda_stream), "rtk_tie_metrics_f64")
             n_batches += 1
     acc = acc.cpu().tolist()
+    tie_sums = tie_acc.cpu().tolist() if rank_type is not None else None
     check_device_errors(device)
+    if rank_type is not None:
+        return _tie_metrics(tie_sums, rank_type, n), acc[4] / n_batches
     sums = {"mrr": acc[0] / n, "hits@1": acc[1] / n, "hits@3": acc[2] / n, "hits@10": acc[3] / n}
     return sums, acc[4] / n_batches

@@ -1335,7 +1335,7 @@ def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=Non
 
 @torch.no_grad()
 def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, want_bce=False, sigmoid_mode=None,
-             tables=None):
+             tables=None, rank_type="stable"):
     """Filtered rank of each ``(h, r, t)`` query against every entity -> int32 ``(B,)``, or ``(ranks, bce_rows float64)``
     with ``want_bce`` -- what ``evaluation.filtered_ranks`` gives on ``score_1vN``'s probabilities, without forming the
     (B, N) score matrix (``rtk_score_rank_*``: the kernels of ``rank_targets_block`` and ``rank_counts_block_1vN`` on the
@@ -1344,7 +1344,18 @@ def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, wan
     ``DeviceFilter``): the other known-true objects of each query's pair count as probability 0.  Ranks are those of
     ``filtered_ranks`` over the fp32 ws score kernel's output (bf16 operands: the bf16 kernel's); the default fp32
     kernel differs from it only on ``cg_fifth_group_columns``.  Inference only.  An ``object_idx`` outside [0, N)
-    raises ``IndexError`` by the ``index_check`` policy."""
+    raises ``IndexError`` by the ``index_check`` policy.
+
+    ``rank_type``: "stable" (the default) is the rank above, the position in a stable descending sort.  "optimistic",
+    "realistic" and "pessimistic" give float64 ranks from the tie counts instead (``rank_ties_1vN``,
+    ``ranks_from_tie_counts``); they do not go with ``want_bce``."""
+    _check_rank_type(rank_type)
+    if rank_type != "stable":
+        if want_bce:
+            raise ValueError(f"want_bce goes with rank_type='stable' only, not {rank_type!r}")
+        greater, equal = rank_ties_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=flt,
+                                       sigmoid_mode=sigmoid_mode, tables=tables)
+        return ranks_from_tie_counts(greater, equal, rank_type)
     nt, nh = torch.as_tensor(object_idx).numel(), torch.as_tensor(subject_idx).numel()
     if nt != nh:
         raise RuntimeError(f"object_idx has {nt} entries for {nh} queries")
@@ -1480,6 +1491,80 @@ def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, s
             flags, counts.data_ptr(), bce.data_ptr() if want_bce else None, ws.data_ptr(), ws.numel(), sp),
             "rtk_score_rank_counts")
     return (counts, bce) if want_bce else counts
+
+
+RANK_TYPES = ("stable", "optimistic", "realistic", "pessimistic")
+
+
+def _check_rank_type(rank_type):
+    if rank_type not in RANK_TYPES:
+        raise ValueError(f"rank_type = {rank_type!r}: one of 'stable', 'optimistic', 'realistic', 'pessimistic'")
+
+
+def ranks_from_tie_counts(greater, equal, rank_type):
+    """The rank of the given type from the two tie counts -> float64: optimistic ``1 + greater``, pessimistic
+    ``1 + greater + equal``, realistic their mean ``1 + greater + equal / 2``.  (The stable rank needs the ids of the
+    tied competitors, not only their number: ``rank_1vN`` returns it.)"""
+    if rank_type == "stable" or rank_type not in RANK_TYPES:
+        raise ValueError(f"rank_type = {rank_type!r}: the tie counts give 'optimistic', 'realistic' or 'pessimistic' "
+                         "ranks ('stable' is rank_1vN's own)")
+    g, e = torch.as_tensor(greater).to(torch.float64), torch.as_tensor(equal).to(torch.float64)
+    share = {"optimistic": 0.0, "realistic": 0.5, "pessimistic": 1.0}[rank_type]
+    return 1.0 + g + share * e
+
+
+@torch.no_grad()
+def rank_tie_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, slots=None, sigmoid_mode=None):
+    """This block's share of the two counts every tie-aware rank derives from (``rtk_score_rank_tie_counts_*``) ->
+    ``(greater, equal)``, int32 ``(B,)`` each: the entities j != t of the block with ``p'_j > pt`` and with
+    ``p'_j == pt`` (IEEE comparison; a NaN never counts).  Arguments, filter rule and exactness as
+    ``rank_counts_block_1vN``: summed over any partition of [0, n_ent) into blocks the counts equal the whole range's,
+    and ``1 + greater <= rank_1vN <= 1 + greater + equal``."""
+    b = _Block(qp, B, O_loc, col0, n_ent, object_idx)
+    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
+    if (not isinstance(pt, torch.Tensor) or pt.dtype != torch.float32 or pt.device != b.dev or pt.numel() != b.B):
+        raise RuntimeError(f"pt must be a float32 tensor of {b.B} target scores on {b.dev}")
+    pt = pt.contiguous().view(-1)
+    slots, _ = _block_filter(b, flt, slots)
+    greater = torch.empty(b.B, dtype=torch.int32, device=b.dev)
+    equal = torch.empty(b.B, dtype=torch.int32, device=b.dev)
+    if b.B == 0:
+        return greater, equal
+    with torch.cuda.device(b.dev):
+        sp = _stream_ptr(b.dev)
+        ws = _workspace(b.dev, sp, _size("rtk_score_rank_ties_workspace_bytes", b.dcode, b.B, b.n_loc, b.c))
+        _lib.check(_entry("rtk_score_rank_tie_counts", b.bf16)(
+            b.qp.data_ptr(), b.B, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent, pt.data_ptr(), b.t.data_ptr(),
+            slots.data_ptr() if flt is not None else None,
+            flt.pair_ptr.data_ptr() if flt is not None else None,
+            flt.pair_obj.data_ptr() if flt is not None else None,
+            flags, greater.data_ptr(), equal.data_ptr(), ws.data_ptr(), ws.numel(), sp),
+            "rtk_score_rank_tie_counts")
+    return greater, equal
+
+
+@torch.no_grad()
+def rank_ties_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, sigmoid_mode=None, tables=None):
+    """The tie counts of each ``(h, r, t)`` query against every entity, without the (B, N) score matrix ->
+    ``(greater, equal)`` int32 ``(B,)``: the one-block call (``rank_targets_block``, then
+    ``rank_tie_counts_block_1vN``, at ``col0 = 0``).  ``equal > 0`` marks a query whose rank the tie rule decides;
+    ``ranks_from_tie_counts`` turns the counts into optimistic, realistic or pessimistic ranks.  Operands, filter and
+    error policy as ``rank_1vN``."""
+    nt, nh = torch.as_tensor(object_idx).numel(), torch.as_tensor(subject_idx).numel()
+    if nt != nh:
+        raise RuntimeError(f"object_idx has {nt} entries for {nh} queries")
+    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    B, N, dev = op.B, op.O.shape[0], op.dev
+    t = _idx("object_idx", object_idx, dev)
+    if B == 0:
+        return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
+    slots = flt.slots_of(op.h, op.r) if flt is not None else None
+    with torch.cuda.device(dev):
+        sp = _stream_ptr(dev)
+        qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.c))
+        _stage1(op, sp, tables, None, qp)
+        pt = rank_targets_block(qp, B, op.O, 0, N, t, sigmoid_mode=sigmoid_mode)
+        return rank_tie_counts_block_1vN(qp, B, op.O, 0, N, pt, t, flt=flt, slots=slots, sigmoid_mode=sigmoid_mode)
 
 
 # Workspace bound of one rtk_score_topk_* call: topk_block_1vN takes the queries in chunks (multiples of the 32-query

@@ -327,6 +327,40 @@ class ShardedEntityScorer:
         ranks = counts + 1
         return (ranks, bce) if want_bce else ranks
 
+    def rank_ties_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt=None, tables=None,
+                      sigmoid_mode=None, targets_fn=None, tie_counts_fn=None):
+        """The tie counts ``(greater, equal)`` (int32, B) of ``ops.rank_ties_1vN`` on entity shards, without the
+        (B, n_loc) score block: ``rank_1vN``'s steps with ``ops.rank_tie_counts_block_1vN`` as the second -- one
+        all-reduce(MAX) of B floats for the target scores, one all-reduce(SUM) of a (2, B) int32 tensor for both
+        counts.  Equals ``ops.rank_ties_1vN`` on the whole entity matrix exactly; a rank without rows contributes
+        zeros and still takes part in both all-reduces.
+
+        ``targets_fn`` / ``tie_counts_fn`` take the arguments of the two ``ops`` functions; tests inject CPU functions
+        (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
+        if targets_fn is None or tie_counts_fn is None:
+            from .ops import rank_targets_block, rank_tie_counts_block_1vN
+            targets_fn = targets_fn or rank_targets_block
+            tie_counts_fn = tie_counts_fn or rank_tie_counts_block_1vN
+        B = int(subject_idx.numel())
+        dev = core.device
+        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
+        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
+        slots = flt.slots_of(subject_idx, relation_idx) if flt is not None else None
+        qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)
+        rows = O_loc[:n_valid] if n_valid > 0 else None
+        pt = (targets_fn(qp, B, rows, lo, self.shards.n_ent, object_idx, sigmoid_mode=sigmoid_mode) if rows is not None
+              else torch.full((B,), float("-inf"), dtype=torch.float32, device=dev))
+        if self.world > 1:
+            dist.all_reduce(pt, op=dist.ReduceOp.MAX, group=self.group)
+        both = torch.zeros((2, B), dtype=torch.int32, device=dev)
+        if rows is not None:
+            greater, equal = tie_counts_fn(qp, B, rows, lo, self.shards.n_ent, pt, object_idx, flt=flt, slots=slots,
+                                           sigmoid_mode=sigmoid_mode)
+            both[0], both[1] = greater, equal
+        if self.world > 1:
+            dist.all_reduce(both, op=dist.ReduceOp.SUM, group=self.group)
+        return both[0], both[1]
+
     # ---- the training loss without the gather and without the score block ----------------------
     def bce_loss_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0,
                      sigmoid_mode=None, max_pos=None, rows_fn=None, grad_o_fn=None, stage1_bwd_fn=None):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Kernel times of filtered ranking without the score matrix (ops.rank_1vN: target_kernel, count_kernel,
-filter_kernel, finish_kernel)
+filter_kernel, finish_kernel) and of the tie counts (ops.rank_ties_1vN: the same kernels in their tie form)
 next to the stored path it replaces (score_1vN + filtered_ranks); run under ``rocprofv3 --kernel-trace --stats`` for the
 per-kernel durations.
 
@@ -48,6 +48,7 @@ with rt.index_check("off"), torch.no_grad():
     res["rank_1vN (WN18RR, tables)"] = timed(lambda: rt.rank_1vN(core, R, S, O, h, r, o, flt=flt, tables=tables))
     res["rank_1vN +bce (WN18RR, tables)"] = timed(
         lambda: rt.rank_1vN(core, R, S, O, h, r, o, flt=flt, want_bce=True, tables=tables))
+    res["rank_ties_1vN (WN18RR, tables)"] = timed(lambda: rt.rank_ties_1vN(core, R, S, O, h, r, o, flt=flt, tables=tables))
     res["score_1vN + filtered_ranks (WN18RR, tables)"] = timed(
         lambda: rt.filtered_ranks(rt.score_1vN(core, R, S, O, h, r, tables=tables), o, flt, items))
 
@@ -60,6 +61,7 @@ with rt.index_check("off"), torch.no_grad():
                   torch.randint(0, N, (B,), device="cuda", generator=g))
     tab = rt.relation_tables(coreb, Rb)
     res["rank_1vN (FB15k-237-like bf16, B 2048)"] = timed(lambda: rt.rank_1vN(coreb, Rb, Eb, Eb, hb, rb, tb, tables=tab))
+    res["rank_ties_1vN (FB15k-237-like bf16, B 2048)"] = timed(lambda: rt.rank_ties_1vN(coreb, Rb, Eb, Eb, hb, rb, tb, tables=tab))
     res["score_1vN + filtered_ranks (bf16, B 2048)"] = timed(
         lambda: rt.filtered_ranks(rt.score_1vN(coreb, Rb, Eb, Eb, hb, rb, tables=tab), tb))
     del Eb
@@ -76,3 +78,5 @@ with rt.index_check("off"), torch.no_grad():
 torch.cuda.synchronize()
 for name, us in res.items():
     print(f"{name:48s} {us:12.1f} us (wall clock, mean)")
+for shape in ("(WN18RR, tables)", "(FB15k-237-like bf16, B 2048)"):
+    print(f"rank_ties_1vN / rank_1vN {shape}: {res['rank_ties_1vN ' + shape] / res['rank_1vN ' + shape]:.3f}")
