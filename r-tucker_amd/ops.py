@@ -577,6 +577,16 @@ class _BceLoss1vN(torch.autograd.Function):
 _STREAM_MAX_C = 208
 
 
+def _csr_slots(flt, item_ids, dev, max_pos=0):
+    """``(pair_slot, max_pos)``: the filter's CSR slot of every item of the batch, and the bound on the CSR entries of its
+    queries, for ``max_pos=None`` ``B * flt.max_list``, which always holds (a filter without ``max_list``: all it has)."""
+    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
+    if max_pos is None:
+        mx = getattr(flt, "max_list", None)
+        max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+    return slot, int(max_pos)
+
+
 def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, matrix_free=False,
                  sigmoid_mode=None, max_pos=None):
     """The reference's training loss term ``nn.BCELoss()(score_fn(T), targets)`` (train.py:79,136) for a
@@ -596,7 +606,7 @@ def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_
                            label_smoothing, sigmoid_mode, max_pos, None, who="bce_loss_1vN(matrix_free=True)")
     if sigmoid_mode is not None or max_pos is not None:
         raise ValueError("sigmoid_mode and max_pos belong to matrix_free=True")
-    slot = flt.slot_of_item[item_ids.to(core.device)].contiguous()
+    slot, _ = _csr_slots(flt, item_ids, core.device)
     return _BceLoss1vN.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                              float(label_smoothing))
 
@@ -675,6 +685,39 @@ class _HipBlockLoss:
         return _stage1_backward(core, R, S, h, r, dv, needs)
 
 
+def _block_enter(ctx, steps, core, R, S, O_loc, subject_idx, relation_idx, eps, max_pos, col0, n_ent, all_reduce, who):
+    """What the forwards of the two block losses begin with: the checked operands ``(core, R, S, O_loc, h, r)``, and on
+    ``ctx`` what their backwards share.  -> ``(operands, zero)``; ``zero`` is the loss of an empty batch (None otherwise)."""
+    operands = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who)
+    core = operands[0]
+    # float32 like the matrix forms; float64 stand-ins of the steps (tests on the CPU) keep their precision
+    ctx.ldt = torch.float64 if core.dtype == torch.float64 else torch.float32
+    ctx.eps, ctx.max_pos, ctx.B, ctx.dv_saved = float(eps), int(max_pos), operands[4].numel(), False
+    ctx.col0, ctx.n_ent, ctx.all_reduce, ctx.steps = col0, n_ent, all_reduce, steps
+    if ctx.B > 0:
+        return operands, None
+    ctx.save_for_backward(*operands[:4])
+    return operands, torch.zeros((), dtype=ctx.ldt, device=core.device)
+
+
+def _zero_batch_grads(ctx):
+    """The backward of an empty batch (core, R, S, O saved): zero gradients for the operands that want one."""
+    needs = ctx.needs_input_grad
+    return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * (len(needs) - 4)
+
+
+def _finish_dv(ctx, dv, g, needs):
+    """``(g_core, g_R, g_S)`` from a block's unscaled dv: dv, (B, c), never gS, (n_ent, b), is summed over the ranks (on
+    a copy where it is the forward's saved share, which stays as it is), then ``g`` and the (linear) stage-1 backward."""
+    if not any(needs[:3]):
+        return None, None, None
+    core, R, S, _, h, r = ctx.saved_tensors[:6]
+    if ctx.all_reduce is not None:
+        dv = dv.clone() if ctx.dv_saved else dv
+        ctx.all_reduce(dv)
+    return tuple(ctx.steps.stage1_backward(core, R, S, h, r, dv * g, needs))
+
+
 class _BceLossBlock(torch.autograd.Function):
     """``_BceLoss1vN`` without the score matrix (``rtk_bce_stream_*_part_f32``), on rows ``[col0, col0 + n_local)`` of the
     entity matrix: sweep 1 (loss rows and dv) in the forward, sweep 2 (gO) in the backward.  What is saved is of size
@@ -686,15 +729,12 @@ class _BceLossBlock(torch.autograd.Function):
     @staticmethod
     def forward(ctx, core, R, S, O_loc, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, max_pos,
                 want_dv, col0, n_ent, all_reduce, steps, who="bce_loss_block_1vN"):
-        core, R, S, O_loc, h, r = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who)
-        B, (n_local, c), dev = h.numel(), O_loc.shape, core.device
-        # float32 like _BceLoss1vN; float64 stand-ins of the steps (tests on the CPU) keep their precision
-        ctx.ldt = ldt = torch.float64 if core.dtype == torch.float64 else torch.float32
-        ctx.eps, ctx.max_pos, ctx.B, ctx.mode, ctx.who = float(eps), int(max_pos), B, sigmoid_mode, who
-        ctx.col0, ctx.n_ent, ctx.all_reduce, ctx.steps, ctx.has_dv = col0, n_ent, all_reduce, steps, want_dv
-        if B == 0:
-            ctx.save_for_backward(core, R, S, O_loc)
-            return torch.zeros((), dtype=ldt, device=dev)
+        (core, R, S, O_loc, h, r), zero = _block_enter(ctx, steps, core, R, S, O_loc, subject_idx, relation_idx, eps, max_pos,
+                                                       col0, n_ent, all_reduce, who)
+        if zero is not None:
+            return zero
+        ctx.mode, ctx.who, ctx.dv_saved = sigmoid_mode, who, want_dv
+        B, (n_local, c), dev, ldt = ctx.B, O_loc.shape, core.device, ctx.ldt
         v = qp = None
         if n_local > 0:
             v, qp = steps.queries(core, R, S, h, r)
@@ -711,35 +751,26 @@ class _BceLossBlock(torch.autograd.Function):
     def backward(ctx, grad_loss):
         needs = ctx.needs_input_grad
         if ctx.B == 0:
-            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 14
-        core, R, S, O_loc, h, r, v, qp, pair_slot, pair_ptr, pair_obj, dv = ctx.saved_tensors
-        steps, B, dev = ctx.steps, ctx.B, core.device
-        g = (grad_loss.to(device=dev, dtype=ctx.ldt).reshape(1) * (1.0 / (B * ctx.n_ent))).contiguous()
-        gcore = gR = gS = gO = None
+            return _zero_batch_grads(ctx)
+        _, _, _, O_loc, _, _, v, qp, pair_slot, pair_ptr, pair_obj, dv = ctx.saved_tensors
+        B = ctx.B
+        g = (grad_loss.to(device=O_loc.device, dtype=ctx.ldt).reshape(1) * (1.0 / (B * ctx.n_ent))).contiguous()
+        gO = None
         if needs[3]:
-            gO = (steps.grad_o(qp, v, B, O_loc, ctx.col0, ctx.n_ent, pair_slot, pair_ptr, pair_obj, ctx.max_pos, ctx.eps,
-                               ctx.mode, g) if O_loc.shape[0] > 0 else torch.zeros_like(O_loc))
-        if any(needs[:3]):
-            if not ctx.has_dv:
-                raise RuntimeError(f"{ctx.who}: dv was not computed in the forward")
-            if ctx.all_reduce is not None:       # dv, (B, c), never gS, (n_ent, b); the saved share stays as it is
-                dv = dv.clone()
-                ctx.all_reduce(dv)
-            gcore, gR, gS = steps.stage1_backward(core, R, S, h, r, dv * g, needs)
-        return (gcore, gR, gS, gO) + (None,) * 14
+            gO = (ctx.steps.grad_o(qp, v, B, O_loc, ctx.col0, ctx.n_ent, pair_slot, pair_ptr, pair_obj, ctx.max_pos, ctx.eps,
+                                   ctx.mode, g) if O_loc.shape[0] > 0 else torch.zeros_like(O_loc))
+        if any(needs[:3]) and not ctx.dv_saved:
+            raise RuntimeError(f"{ctx.who}: dv was not computed in the forward")
+        return _finish_dv(ctx, dv, g, needs) + (gO,) + (None,) * 14
 
 
 def _block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing,
                 sigmoid_mode, max_pos, all_reduce, who="bce_loss_block_1vN"):
-    dev = core.device
-    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-    if max_pos is None:
-        mx = getattr(flt, "max_list", None)
-        max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
+    slot, max_pos = _csr_slots(flt, item_ids, core.device, max_pos)
     # dv (the second tile product of sweep 1) only when a gradient of core, R or S can be asked for
     want_dv = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S))
     return _BceLossBlock.apply(core, R, S, O_loc, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
-                               float(label_smoothing), sigmoid_mode, int(max_pos), want_dv, int(col0), int(n_ent),
+                               float(label_smoothing), sigmoid_mode, max_pos, want_dv, int(col0), int(n_ent),
                                all_reduce, steps, who)
 
 
@@ -796,7 +827,7 @@ class _CeLoss1vN(torch.autograd.Function):
     def backward(ctx, grad_loss):
         needs = ctx.needs_input_grad
         if ctx.B == 0:
-            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 6
+            return _zero_batch_grads(ctx)
         core, R, S, O, h, r, v, Z, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
         if getattr(ctx, "spent", False):
             raise RuntimeError("ce_loss_1vN: backward called twice (the saved logits are overwritten by the first pass)")
@@ -812,64 +843,6 @@ class _CeLoss1vN(torch.autograd.Function):
                                            1.0 / B, _stream_ptr(dev)), "rtk_ce_grad_f32")
         # |dZ| = |w softmax - y| |g| / B <= |g| / B: the operand bound of the split-fp16 GEMMs, no pass over dZ
         return _grads_from_dZ(core, R, S, O, h, r, v, Z, needs, core.dtype, dz_bound=g.abs() * (1.0 / B)) + (None,) * 6
-
-
-class _CeLossStream(torch.autograd.Function):
-    """``_CeLoss1vN`` without the logit matrix (``rtk_ce_stream_*``): one sweep (loss rows and lse) in the forward, two
-    (dv, gO) in the backward.  What is saved is of size B x c and B: the fp32 query vectors, their packed planes, lse."""
-
-    @staticmethod
-    def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, max_pos):
-        who = "ce_loss_1vN(matrix_free=True)"
-        core, R, S, O, h, r = _HipBlockLoss.operands(core, R, S, O, subject_idx, relation_idx, 0, O.shape[0], who)
-        ctx.B = B = h.numel()
-        ctx.eps, ctx.max_pos = float(eps), int(max_pos)
-        dev = core.device
-        if B == 0:
-            ctx.save_for_backward(core, R, S, O)
-            return torch.zeros((), dtype=torch.float32, device=dev)
-        lib = _lib.load()
-        N, c = O.shape
-        v, qp = _HipBlockLoss.queries(core, R, S, h, r)
-        rows = torch.empty(B, dtype=torch.float64, device=dev)
-        lse = torch.empty(B, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            sp = _stream_ptr(dev)
-            ws = _workspace(dev, sp, _size("rtk_ce_stream_workspace_bytes", B, N, c, 0))
-            _lib.check(lib.rtk_ce_stream_rows_f32(qp.data_ptr(), B, c, O.data_ptr(), N, pair_slot.data_ptr(),
-                                                  pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, rows.data_ptr(),
-                                                  lse.data_ptr(), ws.data_ptr(), ws.numel(), sp), "rtk_ce_stream_rows_f32")
-        ctx.save_for_backward(core, R, S, O, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj)
-        return (rows.sum() / B).to(torch.float32)
-
-    @staticmethod
-    def backward(ctx, grad_loss):
-        needs = ctx.needs_input_grad
-        if ctx.B == 0:
-            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 7
-        core, R, S, O, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
-        lib = _lib.load()
-        B, dev = ctx.B, core.device
-        N, c = O.shape
-        g = (grad_loss.to(device=dev, dtype=torch.float32).reshape(1) * (1.0 / B)).contiguous()
-        want_dv = any(needs[:3])
-        gcore = gR = gS = None
-        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
-        gO = torch.empty((N, c), dtype=torch.float32, device=dev) if needs[3] else None
-        if want_dv or needs[3]:
-            max_pos = ctx.max_pos if needs[3] else 0
-            with torch.cuda.device(dev):
-                sp = _stream_ptr(dev)
-                ws = _workspace(dev, sp, _size("rtk_ce_stream_workspace_bytes", B, N, c, max_pos))
-                _lib.check(lib.rtk_ce_stream_grad_f32(qp.data_ptr(), v.data_ptr(), B, c, O.data_ptr(), N, pair_slot.data_ptr(),
-                                                      pair_ptr.data_ptr(), pair_obj.data_ptr(), max_pos, ctx.eps,
-                                                      lse.data_ptr(), g.data_ptr(), dv.data_ptr() if want_dv else None,
-                                                      gO.data_ptr() if needs[3] else None, ws.data_ptr(), ws.numel(), sp),
-                           "rtk_ce_stream_grad_f32")
-                _strict_check(ws, sp)
-        if want_dv:
-            gcore, gR, gS = _stage1_backward(core, R, S, h, r, dv * g, needs)
-        return (gcore, gR, gS, gO) + (None,) * 7
 
 
 def ce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, matrix_free=False,
@@ -889,34 +862,29 @@ def ce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_s
 
     ``matrix_free=False``: on the stored logits of ``score_1vN(sigmoid=False)`` (``rtk_ce_rows_f32`` /
     ``rtk_ce_grad_f32``), float32 operands at any object rank; one backward per forward.
-    ``matrix_free=True``: the same loss and gradients without the (B, N) matrix (``rtk_ce_stream_*``): what is kept
-    between forward and backward is B x c and B.  float32 operands with ``c <= 208``, ``c % 4 == 0`` (anything else
-    raises; there is no fallback).  Under ``no_grad`` only the forward sweep runs.  ``max_pos``: an upper bound on the
-    number of CSR entries of the batch's queries (default ``B * flt.max_list``, which always holds)."""
+    ``matrix_free=True``: the same loss and gradients without the (B, N) matrix, as ``ce_loss_block_1vN`` on the whole
+    range (``rtk_ce_stream_rows_part_f32`` / ``rtk_ce_stream_grad_part_f32`` at ``col0 = 0``, the logarithm taken on
+    the B float64 sums): what is kept between forward and backward is B x c and B.  float32 operands with
+    ``c <= 208``, ``c % 4 == 0`` (anything else raises; there is no fallback).  Under ``no_grad`` only the forward sweep
+    runs.  ``max_pos``: an upper bound on the number of CSR entries of the batch's queries (default
+    ``B * flt.max_list``, which always holds)."""
     _require_gpu("core", core)
-    dev = core.device
-    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-    if matrix_free:
-        if max_pos is None:
-            mx = getattr(flt, "max_list", None)
-            max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
-        return _CeLossStream.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
-                                   float(label_smoothing), int(max_pos))
+    if matrix_free:                      # the whole matrix is one block: col0 = 0, n_ent = N, nothing to exchange
+        return _ce_block_loss(_HipCeBlockLoss, core, R, S, O, 0, O.shape[0], subject_idx, relation_idx, flt, item_ids,
+                              label_smoothing, max_pos, None, None, None, who="ce_loss_1vN(matrix_free=True)")
     if max_pos is not None:
         raise ValueError("max_pos belongs to matrix_free=True")
     if core.dtype != torch.float32:
         raise RuntimeError(f"ce_loss_1vN: float32 operands only, got {core.dtype}")
+    slot, _ = _csr_slots(flt, item_ids, core.device)
     return _CeLoss1vN.apply(core, R, S, O, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                             float(label_smoothing))
 
 
-class _HipCeBlockLoss:
-    """The device steps of the cross-entropy block loss (``rtk_ce_stream_*_part_f32`` around stage 1 and its backward).
-    ``ShardedEntityScorer.ce_loss_1vN`` lets tests put CPU functions with these signatures in their place."""
-
-    operands = staticmethod(_HipBlockLoss.operands)
-    queries = staticmethod(_HipBlockLoss.queries)
-    stage1_backward = staticmethod(_HipBlockLoss.stage1_backward)
+class _HipCeBlockLoss(_HipBlockLoss):
+    """The device steps of the cross-entropy block loss: ``operands``, ``queries`` and ``stage1_backward`` of the BCE
+    steps, with ``rtk_ce_stream_*_part_f32`` between them.  ``ShardedEntityScorer.ce_loss_1vN`` lets tests put CPU
+    functions with these signatures in their place."""
 
     @staticmethod
     def partials(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, eps):
@@ -965,9 +933,9 @@ class _HipCeBlockLoss:
 
 def _ce_row_mass(pair_slot, pair_ptr, eps):
     """w_d = (1 - eps) [n_d > 0] + eps in float64, n_d the STORED list length (0 for pair_slot[d] < 0)."""
-    s = pair_slot.clamp(min=0)
-    n = torch.where(pair_slot >= 0, pair_ptr[s + 1] - pair_ptr[s], torch.zeros_like(s))
-    return (n > 0).to(torch.float64) * (1.0 - eps) + eps
+    ends = pair_ptr.unfold(0, 2, 1)[pair_slot.clamp(min=0)]      # (B, 2), one gather: where each list begins and ends
+    has = (ends[:, 1] > ends[:, 0]) & (pair_slot >= 0)
+    return has.to(torch.float64) * (1.0 - eps) + eps
 
 
 def _ce_empty_partials(B, dev, mdt=torch.float32):
@@ -977,25 +945,22 @@ def _ce_empty_partials(B, dev, mdt=torch.float32):
 
 
 class _CeLossBlock(torch.autograd.Function):
-    """``_CeLossStream`` on rows ``[col0, col0 + n_local)`` of the entity matrix (``rtk_ce_stream_*_part_f32``).  The
-    row's log-sum-exp couples the blocks, so the forward gives the block's ``(m, s, lin)`` and one of three things
-    completes it: the two collectives (MAX of m, SUM of ``[s exp(m - M), lin]``), a given global ``lse`` (the block's
-    share, no collectives) or nothing (the block is the whole range).  The backward is ``grad_part`` with the global
-    lse; with ``all_reduce`` dv is summed over the ranks before the (linear) stage-1 backward.  The gradient of
-    ``O_loc`` is always local.  What is saved is of size B x c and B."""
+    """``_CeLoss1vN`` without the logit matrix (``rtk_ce_stream_*_part_f32``), on rows ``[col0, col0 + n_local)`` of the
+    entity matrix: one sweep in the forward, two (dv, gO) in the backward.  The whole matrix is the block ``col0 = 0,
+    n_ent = N``.  The row's log-sum-exp couples the blocks, so the forward gives the block's ``(m, s, lin)`` and one of
+    three things completes it: the two collectives (MAX of m, SUM of ``[s exp(m - M), lin]``), a given global ``lse``
+    (the block's share, no collectives) or nothing (the block is the whole range).  The backward is ``grad_part`` with
+    the global lse; with ``all_reduce`` dv is summed over the ranks before the (linear) stage-1 backward.  The gradient
+    of ``O_loc`` is always local.  What is saved is of size B x c and B."""
 
     @staticmethod
     def forward(ctx, core, R, S, O_loc, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps, max_pos, col0, n_ent,
                 all_reduce, all_reduce_max, lse, steps, who="ce_loss_block_1vN"):
-        core, R, S, O_loc, h, r = steps.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who)
-        B, (n_local, c), dev = h.numel(), O_loc.shape, core.device
-        # float32 like _CeLossStream; float64 stand-ins of the steps (tests on the CPU) keep their precision
-        ctx.ldt = ldt = torch.float64 if core.dtype == torch.float64 else torch.float32
-        ctx.eps, ctx.max_pos, ctx.B = float(eps), int(max_pos), B
-        ctx.col0, ctx.n_ent, ctx.all_reduce, ctx.steps = col0, n_ent, all_reduce, steps
-        if B == 0:
-            ctx.save_for_backward(core, R, S, O_loc)
-            return torch.zeros((), dtype=ldt, device=dev)
+        (core, R, S, O_loc, h, r), zero = _block_enter(ctx, steps, core, R, S, O_loc, subject_idx, relation_idx, eps, max_pos,
+                                                       col0, n_ent, all_reduce, who)
+        if zero is not None:
+            return zero
+        B, (n_local, c), dev, ldt = ctx.B, O_loc.shape, core.device, ctx.ldt
         v = qp = None
         if n_local > 0:
             v, qp = steps.queries(core, R, S, h, r)
@@ -1016,7 +981,7 @@ class _CeLossBlock(torch.autograd.Function):
             sigma = s * torch.exp(m.to(torch.float64) - lse)
             rows = w * lse * sigma + lin
         else:                                    # the whole range
-            lse = m.to(torch.float64) + torch.log(s)
+            lse = torch.log(s).add_(m)          # float64: m is converted inside the sum
             rows = w * lse + lin
         ctx.save_for_backward(core, R, S, O_loc, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj)
         return (rows.sum() / B).to(ldt)
@@ -1025,32 +990,19 @@ class _CeLossBlock(torch.autograd.Function):
     def backward(ctx, grad_loss):
         needs = ctx.needs_input_grad
         if ctx.B == 0:
-            return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * 14
-        core, R, S, O_loc, h, r, v, qp, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
-        steps, B, dev = ctx.steps, ctx.B, core.device
+            return _zero_batch_grads(ctx)
+        _, _, _, O_loc, _, _, v, qp, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
+        B, dev = ctx.B, O_loc.device
         n_local, c = O_loc.shape
         g = (grad_loss.to(device=dev, dtype=ctx.ldt).reshape(1) * (1.0 / B)).contiguous()
         want_dv = any(needs[:3])
-        gcore = gR = gS = None
         if n_local > 0:
-            dv, gO = steps.grad(qp, v, B, O_loc, ctx.col0, ctx.n_ent, pair_slot, pair_ptr, pair_obj, ctx.max_pos, ctx.eps,
-                                lse, g, want_dv, bool(needs[3]))
+            dv, gO = ctx.steps.grad(qp, v, B, O_loc, ctx.col0, ctx.n_ent, pair_slot, pair_ptr, pair_obj, ctx.max_pos,
+                                    ctx.eps, lse, g, want_dv, bool(needs[3]))
         else:
             dv = torch.zeros((B, c), dtype=ctx.ldt, device=dev) if want_dv else None
             gO = torch.zeros_like(O_loc) if needs[3] else None
-        if want_dv:
-            if ctx.all_reduce is not None:       # dv, (B, c), never gS, (n_ent, b)
-                ctx.all_reduce(dv)
-            gcore, gR, gS = steps.stage1_backward(core, R, S, h, r, dv * g, needs)
-        return (gcore, gR, gS, gO) + (None,) * 14
-
-
-def _ce_slots(flt, item_ids, dev, max_pos):
-    slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-    if max_pos is None:
-        mx = getattr(flt, "max_list", None)
-        max_pos = int(slot.numel()) * int(mx) if mx is not None else int(flt.pair_obj.numel())
-    return slot, int(max_pos)
+        return _finish_dv(ctx, dv, g, needs) + (gO,) + (None,) * 14
 
 
 def _ce_block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids, label_smoothing,
@@ -1060,15 +1012,15 @@ def _ce_block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_
         raise ValueError(f"{who}: all_reduce (SUM) and all_reduce_max (MAX) come together: the forward needs both")
     if lse is not None and all_reduce is not None:
         raise ValueError(f"{who}: lse= (the block's share, no exchange) and the collectives exclude each other")
-    B = int(subject_idx.numel())
     if lse is not None:
+        B = int(subject_idx.numel())
         if not isinstance(lse, torch.Tensor) or lse.dtype != torch.float64 or tuple(lse.shape) != (B,):
             raise ValueError(f"{who}: lse must be the global log-sum-exp as a float64 tensor of shape ({B},)")
         lse = lse.detach().to(core.device).contiguous()
     elif all_reduce is None and not (col0 == 0 and n_local == n_ent):
         raise ValueError(f"{who}: block [{col0}, {col0} + {n_local}) of n_ent = {n_ent} without collectives or lse=: the "
                          "block's own log-sum-exp is not the loss")
-    slot, max_pos = _ce_slots(flt, item_ids, core.device, max_pos)
+    slot, max_pos = _csr_slots(flt, item_ids, core.device, max_pos)
     return _CeLossBlock.apply(core, R, S, O_loc, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                               float(label_smoothing), max_pos, col0, n_ent, all_reduce, all_reduce_max, lse, steps, who)
 
@@ -1088,7 +1040,7 @@ def ce_partials_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_
         B = h.numel()
         if B == 0 or O_loc.shape[0] == 0:
             return _ce_empty_partials(B, core.device)
-        slot, _ = _ce_slots(flt, item_ids, core.device, 0)
+        slot, _ = _csr_slots(flt, item_ids, core.device)
         _, qp = _HipBlockLoss.queries(core, R, S, h, r)
         return _HipCeBlockLoss.partials(qp, B, O_loc, int(col0), int(n_ent), slot, flt.pair_ptr, flt.pair_obj,
                                         float(label_smoothing))
@@ -1462,6 +1414,25 @@ def _block_filter(b, flt, slots, keep_idx=None):
     return slots, keep_idx
 
 
+def _count_step(name, ws_bytes, b, pt, flt, slots, sigmoid_mode, out0, out1):
+    """A counting step on block ``b``: the entry ``name`` (``_f32`` / ``_bf16``; workspace of ``ws_bytes``) on the
+    completed target scores ``pt`` and the filter's CSR (NULLs without ``flt``) into ``out0``, ``out1`` (None: NULL)."""
+    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
+    if (not isinstance(pt, torch.Tensor) or pt.dtype != torch.float32 or pt.device != b.dev or pt.numel() != b.B):
+        raise RuntimeError(f"pt must be a float32 tensor of {b.B} target scores on {b.dev}")
+    pt = pt.contiguous().view(-1)
+    slots, _ = _block_filter(b, flt, slots)
+    csr = (None,) * 3 if flt is None else (slots.data_ptr(), flt.pair_ptr.data_ptr(), flt.pair_obj.data_ptr())
+    if b.B == 0:
+        return
+    with torch.cuda.device(b.dev):
+        sp = _stream_ptr(b.dev)
+        ws = _workspace(b.dev, sp, _size(ws_bytes, b.dcode, b.B, b.n_loc, b.c))
+        _lib.check(_entry(name, b.bf16)(
+            b.qp.data_ptr(), b.B, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent, pt.data_ptr(), b.t.data_ptr(), *csr, flags,
+            out0.data_ptr(), None if out1 is None else out1.data_ptr(), ws.data_ptr(), ws.numel(), sp), name)
+
+
 @torch.no_grad()
 def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, slots=None, want_bce=False,
                           sigmoid_mode=None):
@@ -1471,25 +1442,9 @@ def rank_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=None, s
     other known-true objects count as probability 0.  Summed over any partition of [0, n_ent) into blocks,
     ``1 + counts`` equals ``rank_1vN``'s ranks exactly."""
     b = _Block(qp, B, O_loc, col0, n_ent, object_idx)
-    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
-    if (not isinstance(pt, torch.Tensor) or pt.dtype != torch.float32 or pt.device != b.dev or pt.numel() != b.B):
-        raise RuntimeError(f"pt must be a float32 tensor of {b.B} target scores on {b.dev}")
-    pt = pt.contiguous().view(-1)
-    slots, _ = _block_filter(b, flt, slots)
     counts = torch.empty(b.B, dtype=torch.int32, device=b.dev)
     bce = torch.empty(b.B, dtype=torch.float64, device=b.dev) if want_bce else None
-    if b.B == 0:
-        return (counts, bce) if want_bce else counts
-    with torch.cuda.device(b.dev):
-        sp = _stream_ptr(b.dev)
-        ws = b.workspace(sp)
-        _lib.check(_entry("rtk_score_rank_counts", b.bf16)(
-            b.qp.data_ptr(), b.B, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent, pt.data_ptr(), b.t.data_ptr(),
-            slots.data_ptr() if flt is not None else None,
-            flt.pair_ptr.data_ptr() if flt is not None else None,
-            flt.pair_obj.data_ptr() if flt is not None else None,
-            flags, counts.data_ptr(), bce.data_ptr() if want_bce else None, ws.data_ptr(), ws.numel(), sp),
-            "rtk_score_rank_counts")
+    _count_step("rtk_score_rank_counts", "rtk_score_rank_part_workspace_bytes", b, pt, flt, slots, sigmoid_mode, counts, bce)
     return (counts, bce) if want_bce else counts
 
 
@@ -1521,25 +1476,10 @@ def rank_tie_counts_block_1vN(qp, B, O_loc, col0, n_ent, pt, object_idx, flt=Non
     ``rank_counts_block_1vN``: summed over any partition of [0, n_ent) into blocks the counts equal the whole range's,
     and ``1 + greater <= rank_1vN <= 1 + greater + equal``."""
     b = _Block(qp, B, O_loc, col0, n_ent, object_idx)
-    flags = _score_flags(True, sigmoid_mode, torch.float32, b.bf16)
-    if (not isinstance(pt, torch.Tensor) or pt.dtype != torch.float32 or pt.device != b.dev or pt.numel() != b.B):
-        raise RuntimeError(f"pt must be a float32 tensor of {b.B} target scores on {b.dev}")
-    pt = pt.contiguous().view(-1)
-    slots, _ = _block_filter(b, flt, slots)
     greater = torch.empty(b.B, dtype=torch.int32, device=b.dev)
     equal = torch.empty(b.B, dtype=torch.int32, device=b.dev)
-    if b.B == 0:
-        return greater, equal
-    with torch.cuda.device(b.dev):
-        sp = _stream_ptr(b.dev)
-        ws = _workspace(b.dev, sp, _size("rtk_score_rank_ties_workspace_bytes", b.dcode, b.B, b.n_loc, b.c))
-        _lib.check(_entry("rtk_score_rank_tie_counts", b.bf16)(
-            b.qp.data_ptr(), b.B, b.c, b.O.data_ptr(), b.n_loc, b.col0, b.n_ent, pt.data_ptr(), b.t.data_ptr(),
-            slots.data_ptr() if flt is not None else None,
-            flt.pair_ptr.data_ptr() if flt is not None else None,
-            flt.pair_obj.data_ptr() if flt is not None else None,
-            flags, greater.data_ptr(), equal.data_ptr(), ws.data_ptr(), ws.numel(), sp),
-            "rtk_score_rank_tie_counts")
+    _count_step("rtk_score_rank_tie_counts", "rtk_score_rank_ties_workspace_bytes", b, pt, flt, slots, sigmoid_mode, greater,
+                equal)
     return greater, equal
 
 

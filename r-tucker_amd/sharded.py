@@ -150,6 +150,36 @@ class ShardedEntityScorer:
             self._gathered = g
         return g
 
+    def _real_rows(self):
+        """``(lo, n_valid)``: this rank's rows of ``O_loc`` that are entities, ``[lo, lo + n_valid)`` of the entity
+        matrix.  The last shard's padding rows are not entities, and a rank that lies wholly past ``n_ent`` has none."""
+        lo, hi = self.shards.bounds(self.rank)
+        return lo, hi - lo
+
+    def _all_reduce(self, op):
+        """``fn(t)``, the all-reduce of ``t`` in place over the group; None at world size 1, where nothing is exchanged."""
+        if self.world == 1:
+            return None
+        return lambda t: dist.all_reduce(t, op=op, group=self.group)
+
+    def _loss_steps(self, default, dtype, **injected):
+        """The steps of a block loss: the class ``default`` of ``ops``, or, when a test injects CPU functions (the
+        ``injected`` steps by name, ``query_vectors_fn`` / ``pack_fn`` for stage 1), a namespace that has them in the
+        default steps' places and checks no operands."""
+        if not any(injected.values()) and self.query_vectors_fn is None:
+            return default
+        from types import SimpleNamespace
+        from .ops import pack_query_vectors
+
+        def queries(core, R, S, h, r):
+            v = self.query_vectors_fn(core, R, S, h, r)
+            return v, (self.pack_fn or pack_query_vectors)(v, dtype)
+
+        return SimpleNamespace(
+            operands=lambda c_, R_, S_, O_, h, r, col0, n, who: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
+            queries=queries if self.query_vectors_fn is not None else default.queries,
+            **{name: fn or getattr(default, name) for name, fn in injected.items()})
+
     def _split_stage1(self, core) -> bool:
         if self.world == 1 or self.stage1 == "replicated":
             return False
@@ -246,22 +276,25 @@ class ShardedEntityScorer:
             target_scores_fn = target_scores_fn or target_scores_block
             rank_counts_fn = rank_counts_fn or rank_counts_block
         B = int(subject_idx.numel())
-        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
-        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
+        lo, n_valid = self._real_rows()
         g = self._buffer(B, core.device, torch.float32)      # the ranking kernels read fp32 scores
-        mine = g[self.rank][:, :n_loc]
+        mine = g[self.rank][:, :self.shards.n_loc]
         self._score_local(core, R, S, O_loc, subject_idx, relation_idx, mine, **kw)
         block = mine[:, :n_valid] if n_valid > 0 else None
         pt = (target_scores_fn(block, object_idx, lo) if block is not None
               else torch.full((B,), float("-inf"), dtype=torch.float32, device=core.device))
         if self.world > 1:
             dist.all_reduce(pt, op=dist.ReduceOp.MAX, group=self.group)
-        if block is not None:
-            res = rank_counts_fn(block, object_idx, lo, pt, flt, item_ids, want_bce)
-            counts, bce = res if want_bce else (res, None)
-        else:
-            counts = torch.zeros(B, dtype=torch.int32, device=core.device)
-            bce = torch.zeros(B, dtype=torch.float64, device=core.device) if want_bce else None
+        res = rank_counts_fn(block, object_idx, lo, pt, flt, item_ids, want_bce) if block is not None else None
+        return self._ranks_from_counts(res, B, core.device, want_bce)
+
+    def _ranks_from_counts(self, res, B, device, want_bce):
+        """Ranks from the block's ``counts`` or ``(counts, bce)`` (None: a rank without rows, which counts nothing): one
+        all-reduce(SUM) of B int32 (+ B doubles for the BCE sums), rank = count + 1."""
+        if res is None:
+            res = torch.zeros(B, dtype=torch.int32, device=device)
+            res = (res, torch.zeros(B, dtype=torch.float64, device=device)) if want_bce else res
+        counts, bce = res if want_bce else (res, None)
         if self.world > 1:
             dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
             if want_bce:
@@ -288,6 +321,23 @@ class ShardedEntityScorer:
             from .ops import pack_query_vectors as pack
         return pack(v, dtype)
 
+    def _rank_targets(self, core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt, tables, sigmoid_mode, targets_fn):
+        """The first step of ``rank_1vN`` and ``rank_ties_1vN`` -> ``(qp, rows, lo, slots, pt)``: the packed query planes,
+        this rank's real rows of ``O_loc`` (None for a rank without rows) and their first global row, the queries' filter
+        slots, and the target scores completed by one all-reduce(MAX) of B floats."""
+        if targets_fn is None:
+            from .ops import rank_targets_block as targets_fn
+        B = int(subject_idx.numel())
+        lo, n_valid = self._real_rows()
+        slots = flt.slots_of(subject_idx, relation_idx) if flt is not None else None
+        qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)
+        rows = O_loc[:n_valid] if n_valid > 0 else None
+        pt = (targets_fn(qp, B, rows, lo, self.shards.n_ent, object_idx, sigmoid_mode=sigmoid_mode) if rows is not None
+              else torch.full((B,), float("-inf"), dtype=torch.float32, device=core.device))
+        if self.world > 1:
+            dist.all_reduce(pt, op=dist.ReduceOp.MAX, group=self.group)
+        return qp, rows, lo, slots, pt
+
     def rank_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt=None, want_bce=False, tables=None,
                  sigmoid_mode=None, targets_fn=None, counts_fn=None):
         """``filtered_ranks`` without the (B, n_loc) score block: stage 1 once into packed query planes, the target
@@ -298,34 +348,14 @@ class ShardedEntityScorer:
 
         ``targets_fn`` / ``counts_fn`` take the arguments of the two ``ops`` functions; tests inject CPU functions
         (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
-        if targets_fn is None or counts_fn is None:
-            from .ops import rank_counts_block_1vN, rank_targets_block
-            targets_fn = targets_fn or rank_targets_block
-            counts_fn = counts_fn or rank_counts_block_1vN
+        if counts_fn is None:
+            from .ops import rank_counts_block_1vN as counts_fn
         B = int(subject_idx.numel())
-        dev = core.device
-        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
-        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
-        slots = flt.slots_of(subject_idx, relation_idx) if flt is not None else None
-        qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)
-        rows = O_loc[:n_valid] if n_valid > 0 else None
-        pt = (targets_fn(qp, B, rows, lo, self.shards.n_ent, object_idx, sigmoid_mode=sigmoid_mode) if rows is not None
-              else torch.full((B,), float("-inf"), dtype=torch.float32, device=dev))
-        if self.world > 1:
-            dist.all_reduce(pt, op=dist.ReduceOp.MAX, group=self.group)
-        if rows is not None:
-            res = counts_fn(qp, B, rows, lo, self.shards.n_ent, pt, object_idx, flt=flt, slots=slots, want_bce=want_bce,
-                            sigmoid_mode=sigmoid_mode)
-            counts, bce = res if want_bce else (res, None)
-        else:
-            counts = torch.zeros(B, dtype=torch.int32, device=dev)
-            bce = torch.zeros(B, dtype=torch.float64, device=dev) if want_bce else None
-        if self.world > 1:
-            dist.all_reduce(counts, op=dist.ReduceOp.SUM, group=self.group)
-            if want_bce:
-                dist.all_reduce(bce, op=dist.ReduceOp.SUM, group=self.group)
-        ranks = counts + 1
-        return (ranks, bce) if want_bce else ranks
+        qp, rows, lo, slots, pt = self._rank_targets(core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt, tables,
+                                                     sigmoid_mode, targets_fn)
+        res = counts_fn(qp, B, rows, lo, self.shards.n_ent, pt, object_idx, flt=flt, slots=slots, want_bce=want_bce,
+                        sigmoid_mode=sigmoid_mode) if rows is not None else None
+        return self._ranks_from_counts(res, B, core.device, want_bce)
 
     def rank_ties_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt=None, tables=None,
                       sigmoid_mode=None, targets_fn=None, tie_counts_fn=None):
@@ -337,22 +367,12 @@ class ShardedEntityScorer:
 
         ``targets_fn`` / ``tie_counts_fn`` take the arguments of the two ``ops`` functions; tests inject CPU functions
         (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
-        if targets_fn is None or tie_counts_fn is None:
-            from .ops import rank_targets_block, rank_tie_counts_block_1vN
-            targets_fn = targets_fn or rank_targets_block
-            tie_counts_fn = tie_counts_fn or rank_tie_counts_block_1vN
+        if tie_counts_fn is None:
+            from .ops import rank_tie_counts_block_1vN as tie_counts_fn
         B = int(subject_idx.numel())
-        dev = core.device
-        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
-        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
-        slots = flt.slots_of(subject_idx, relation_idx) if flt is not None else None
-        qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)
-        rows = O_loc[:n_valid] if n_valid > 0 else None
-        pt = (targets_fn(qp, B, rows, lo, self.shards.n_ent, object_idx, sigmoid_mode=sigmoid_mode) if rows is not None
-              else torch.full((B,), float("-inf"), dtype=torch.float32, device=dev))
-        if self.world > 1:
-            dist.all_reduce(pt, op=dist.ReduceOp.MAX, group=self.group)
-        both = torch.zeros((2, B), dtype=torch.int32, device=dev)
+        qp, rows, lo, slots, pt = self._rank_targets(core, R, S, O_loc, subject_idx, relation_idx, object_idx, flt, tables,
+                                                     sigmoid_mode, targets_fn)
+        both = torch.zeros((2, B), dtype=torch.int32, device=core.device)
         if rows is not None:
             greater, equal = tie_counts_fn(qp, B, rows, lo, self.shards.n_ent, pt, object_idx, flt=flt, slots=slots,
                                            sigmoid_mode=sigmoid_mode)
@@ -381,28 +401,11 @@ class ShardedEntityScorer:
         ``rows_fn`` / ``grad_o_fn`` / ``stage1_bwd_fn`` take the arguments of ``ops._HipBlockLoss.rows`` / ``grad_o``
         / ``stage1_backward``; tests inject CPU functions (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
         from . import ops
-        n_ent, n_loc = self.shards.n_ent, self.shards.n_loc
-        lo = min(self.rank * n_loc, n_ent)
-        n_valid = max(0, min(n_loc, n_ent - lo))                 # the last shard's padding rows are not entities
-        steps = ops._HipBlockLoss
-        if rows_fn or grad_o_fn or stage1_bwd_fn or self.query_vectors_fn is not None:
-            from types import SimpleNamespace
-
-            def queries(core_, R_, S_, h, r):
-                v = self.query_vectors_fn(core_, R_, S_, h, r)
-                return v, (self.pack_fn or ops.pack_query_vectors)(v, O_loc.dtype)
-
-            steps = SimpleNamespace(
-                operands=lambda c_, R_, S_, O_, h, r, col0, n, who: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
-                queries=queries if self.query_vectors_fn is not None else steps.queries,
-                rows=rows_fn or steps.rows, grad_o=grad_o_fn or steps.grad_o,
-                stage1_backward=stage1_bwd_fn or steps.stage1_backward)
-        reduce = None
-        if self.world > 1:
-            def reduce(t):
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
-        return ops._block_loss(steps, core, R, S, O_loc[:n_valid], lo, n_ent, subject_idx, relation_idx, flt, item_ids,
-                               label_smoothing, sigmoid_mode, max_pos, reduce)
+        lo, n_valid = self._real_rows()
+        steps = self._loss_steps(ops._HipBlockLoss, O_loc.dtype, rows=rows_fn, grad_o=grad_o_fn,
+                                 stage1_backward=stage1_bwd_fn)
+        return ops._block_loss(steps, core, R, S, O_loc[:n_valid], lo, self.shards.n_ent, subject_idx, relation_idx, flt,
+                               item_ids, label_smoothing, sigmoid_mode, max_pos, self._all_reduce(dist.ReduceOp.SUM))
 
     def ce_loss_1vN(self, core, R, S, O_loc, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, max_pos=None,
                     partials_fn=None, grad_fn=None, stage1_bwd_fn=None):
@@ -416,8 +419,9 @@ class ShardedEntityScorer:
         average them again); ``O_loc.grad`` is this rank's rows of the gradient of O and needs no exchange.  The last
         shard's zero padding rows are not entities: they enter neither the log-sum-exp nor the smoothing term and
         their gradient is 0.  A rank without rows contributes ``m = -inf, s = 0, lin = 0`` and zero dv and still takes
-        part in all three exchanges.  Without a process group (world size 1) this is
-        ``ops.ce_loss_1vN(..., matrix_free=True)`` bit for bit.
+        part in all three exchanges.  Every world size runs the same block loss; without a process group (world size 1)
+        nothing is exchanged and the call is the one ``ops.ce_loss_1vN(..., matrix_free=True)`` makes: the whole range as
+        one block.
 
         Stage 1 and its backward stay replicated, as in ``bce_loss_1vN``.
 
@@ -425,36 +429,12 @@ class ShardedEntityScorer:
         ``grad`` / ``stage1_backward``; tests inject CPU functions (with ``query_vectors_fn`` / ``pack_fn`` for
         stage 1)."""
         from . import ops
-        n_ent, n_loc = self.shards.n_ent, self.shards.n_loc
-        lo = min(self.rank * n_loc, n_ent)
-        n_valid = max(0, min(n_loc, n_ent - lo))                 # the last shard's padding rows are not entities
-        steps = ops._HipCeBlockLoss
-        injected = partials_fn or grad_fn or stage1_bwd_fn or self.query_vectors_fn is not None
-        if injected:
-            from types import SimpleNamespace
-
-            def queries(core_, R_, S_, h, r):
-                v = self.query_vectors_fn(core_, R_, S_, h, r)
-                return v, (self.pack_fn or ops.pack_query_vectors)(v, O_loc.dtype)
-
-            steps = SimpleNamespace(
-                operands=lambda c_, R_, S_, O_, h, r, col0, n, who: (c_, R_, S_, O_, h.view(-1), r.view(-1)),
-                queries=queries if self.query_vectors_fn is not None else steps.queries,
-                partials=partials_fn or steps.partials, grad=grad_fn or steps.grad,
-                stage1_backward=stage1_bwd_fn or steps.stage1_backward)
-        if self.world == 1 and not injected:
-            return ops.ce_loss_1vN(core, R, S, O_loc[:n_valid], subject_idx, relation_idx, flt, item_ids,
-                                   label_smoothing, matrix_free=True, max_pos=max_pos)
-        reduce_sum = reduce_max = None
-        if self.world > 1:
-            def reduce_sum(t):
-                dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
-
-            def reduce_max(t):
-                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
-        return ops._ce_block_loss(steps, core, R, S, O_loc[:n_valid], lo, n_ent, subject_idx, relation_idx, flt, item_ids,
-                                  label_smoothing, max_pos, reduce_sum, reduce_max, None,
-                                  who="ShardedEntityScorer.ce_loss_1vN")
+        lo, n_valid = self._real_rows()
+        steps = self._loss_steps(ops._HipCeBlockLoss, O_loc.dtype, partials=partials_fn, grad=grad_fn,
+                                 stage1_backward=stage1_bwd_fn)
+        return ops._ce_block_loss(steps, core, R, S, O_loc[:n_valid], lo, self.shards.n_ent, subject_idx, relation_idx, flt,
+                                  item_ids, label_smoothing, max_pos, self._all_reduce(dist.ReduceOp.SUM),
+                                  self._all_reduce(dist.ReduceOp.MAX), None, who="ShardedEntityScorer.ce_loss_1vN")
 
     # ---- top-k without the gather ----------------------------------------------------------
     def topk(self, core, R, S, O_loc, subject_idx, relation_idx, k, flt=None, slots=None, keep_idx=None,
@@ -482,12 +462,11 @@ class ShardedEntityScorer:
                 P, k_, flt_, keep_idx=keep_, slots=slots_, col0=col0))
             merge_fn = merge_fn or (lambda v, i, k_: filtered_topk(v, k_, ids=i))
         B = int(subject_idx.numel())
-        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
-        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))
+        lo, n_valid = self._real_rows()
         if slots is None and flt is not None:
             slots = flt.slots_of(subject_idx, relation_idx)
         g = self._buffer(B, core.device, self.score_dtype)
-        mine = g[self.rank][:, :n_loc]
+        mine = g[self.rank][:, :self.shards.n_loc]
         self._score_local(core, R, S, O_loc, subject_idx, relation_idx, mine, **kw)
         values, ids = local_topk_fn(mine[:, :n_valid], k, lo, flt, slots, keep_idx)
         return self._merge_topk(values, ids, B, k, merge_fn)
@@ -500,8 +479,7 @@ class ShardedEntityScorer:
             from .evaluation import filtered_topk
             merge_fn = lambda v, i, k_: filtered_topk(v, k_, ids=i)                      # noqa: E731
         B = int(subject_idx.numel())
-        n_loc, lo = self.shards.n_loc, self.rank * self.shards.n_loc
-        n_valid = max(0, min(n_loc, self.shards.n_ent - lo))      # the last shard's padding rows are not entities
+        lo, n_valid = self._real_rows()
         if slots is None and flt is not None:
             slots = flt.slots_of(subject_idx, relation_idx)
         qp = self._packed_queries(core, R, S, O_loc.dtype, subject_idx, relation_idx, tables)

@@ -250,6 +250,50 @@ def test_abi_single_outputs_and_the_max_pos_bound(rt):
     assert err == 0
 
 
+@pytest.mark.parametrize("eps", [0.0, 0.1])
+@pytest.mark.parametrize("n_ent,rank,B", [(500, (3, 16, 16), 16), (3003, (5, 100, 100), 70)])
+def test_the_op_agrees_with_the_whole_matrix_abi(rt, n_ent, rank, B, eps):
+    """ce_loss_1vN(matrix_free=True) is the block loss on the whole range; rtk_ce_stream_rows_f32 / rtk_ce_stream_grad_f32
+    share no host code with it.  gO of (loss * 3).backward() has the bits of the ABI's at scale 3 / B: both end in the
+    same gradient kernels, which see the forward only through float32(lse).  The loss rows are the same float64 terms
+    added in another order (w lse + (lin) against (w lse - t0 sum z) + the positives' part): the float64 row sum moves by
+    a few units of 2^-53 relative, so the float32 loss differs from float32(rows.sum() / B) only where that sits on a
+    rounding boundary, and then by one float32 ulp.  One query of the batch has an empty list."""
+    lib = rt._lib.load()
+    c = rank[2]
+    params, ds, ids, h, r = _case(n_ent, rank, B, 47, eps, True)
+    assert len(ds.objects(int(ids[0]))) == 0
+    flt = rt.DeviceFilter(ds, "cuda")
+    hc, rc, idc = h.cuda(), r.cuda(), torch.from_numpy(ids).cuda()
+    ps = [x.cuda().requires_grad_(True) for x in params]
+    loss = rt.ce_loss_1vN(*ps, hc, rc, flt, idc, label_smoothing=eps, matrix_free=True)
+    (loss * 3.0).backward()
+    O = ps[3].detach()
+    slot = flt.slot_of_item[idc].contiguous()
+    csr = (slot.data_ptr(), flt.pair_ptr.data_ptr(), flt.pair_obj.data_ptr())
+    v, qp = rt.query_vectors(*[p.detach() for p in ps[:3]], hc, rc, packed=True)
+    max_pos = B * flt.max_list
+    sp = torch.cuda.current_stream().cuda_stream
+    rows = torch.empty(B, dtype=torch.float64, device="cuda")
+    lse = torch.empty(B, dtype=torch.float32, device="cuda")
+    sc = torch.tensor([3.0 / B], dtype=torch.float32, device="cuda")
+    gO = torch.full((n_ent, c), -7.0, device="cuda")
+    ws = torch.zeros(lib.rtk_ce_stream_workspace_bytes(B, n_ent, c, max_pos), dtype=torch.uint8, device="cuda")
+    rt._lib.check(lib.rtk_ce_stream_rows_f32(qp.data_ptr(), B, c, O.data_ptr(), n_ent, *csr, eps, rows.data_ptr(),
+                                             lse.data_ptr(), ws.data_ptr(), ws.numel(), sp), "rows")
+    rt._lib.check(lib.rtk_ce_stream_grad_f32(qp.data_ptr(), v.data_ptr(), B, c, O.data_ptr(), n_ent, *csr, max_pos, eps,
+                                             lse.data_ptr(), sc.data_ptr(), None, gO.data_ptr(), ws.data_ptr(), ws.numel(),
+                                             sp), "grad")
+    torch.cuda.synchronize()
+    assert int(ws[:4].view(torch.int32).item()) == 0
+    want = (rows.sum() / B).to(torch.float32)
+    near = [torch.nextafter(want, torch.full_like(want, s)) for s in (float("-inf"), float("inf"))]
+    print(f"loss {loss.item():.9g}  ABI {want.item():.9g}  its neighbours {near[0].item():.9g} {near[1].item():.9g}; "
+          f"gO equal {torch.equal(ps[3].grad, gO)}, max |diff| {(ps[3].grad - gO).abs().max().item():.3e}")
+    assert torch.equal(ps[3].grad, gO)
+    assert any(torch.equal(loss.detach(), x) for x in [want] + near)
+
+
 def test_train_py_short_run_with_the_ce_loss(tmp_path, capsys):
     import train
     state = train.main(["--mode", "asymmetric", "--optim", "rsgd", "--seed", "322", "--data",

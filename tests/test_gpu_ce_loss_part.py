@@ -107,10 +107,19 @@ def test_mode_checks_on_the_device(rt):
     with pytest.raises(RuntimeError, match="is not a part of"):
         rt.ce_loss_block_1vN(*ps[:3], ps[3][100:200], 450, 500, hc, rc, flt, idc,
                              lse=torch.zeros(16, dtype=torch.float64, device="cuda"))
-    # the whole range needs neither lse nor collectives and is the loss
-    whole = rt.ce_loss_block_1vN(*ps, 0, 500, hc, rc, flt, idc, label_smoothing=0.1)
-    ref = rt.ce_loss_1vN(*ps, hc, rc, flt, idc, label_smoothing=0.1, matrix_free=True)
-    assert abs(whole.item() - ref.item()) <= 2e-6 * max(1.0, abs(ref.item()))
+    # the whole range needs neither lse nor collectives and is the loss: ce_loss_1vN(matrix_free=True) is this call
+    runs = []
+    for block in (True, False):
+        leaves = [p.clone().requires_grad_(True) for p in ps]
+        if block:
+            loss = rt.ce_loss_block_1vN(*leaves, 0, 500, hc, rc, flt, idc, label_smoothing=0.1)
+        else:
+            loss = rt.ce_loss_1vN(*leaves, hc, rc, flt, idc, label_smoothing=0.1, matrix_free=True)
+        (loss * 3.0).backward()
+        runs.append([loss.detach()] + [p.grad for p in leaves])
+    assert len(runs[0]) == 5
+    for a, b in zip(*runs):
+        assert torch.equal(a, b)
     # batch == 0: a zero loss and zero gradients; an empty block: a zero share, an empty gradient
     leaves = [p.clone().requires_grad_(True) for p in ps[:3]]
     O_blk = ps[3][100:200].clone().requires_grad_(True)
