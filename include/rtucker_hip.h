@@ -973,6 +973,47 @@ int rtk_ce_stream_grad_part_f32(const void *q_packed, const float *v, int64_t ba
                                 const float *lse, const float *scale, float *dv_out, float *gO_local_out,
                                 void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * Relation prediction (h, ?, t): the third mode of the trilinear form, with the model's own parameters.  For query d
+ * with subject h_d and object t_d
+ *     W[d, i, j] = sum_k G[i, j, k] * O[t_d, k]
+ *     u[d, i]    = sum_j S[h_d, j] * W[d, i, j]        the "pair vector" (batch x a, fp32)
+ *     z[d, r]    = sum_i u[d, i] * R[r, i]             the 1-vs-all logit of (h_d, r) at column t_d
+ * rtk_pair_vectors_* computes u without writing W: the core's a*b rows take O's place in an entity-stationary sweep on
+ * the packed planes of the gathered O[t_d] rows, each 32 x 32 tile of W is multiplied by S[h_d, j] in registers and
+ * reduced over j; only batch * a * ceil(b / 32) partial sums reach the workspace (csrc/rtk_pair.hip).  Symmetric
+ * model: pass E as S and O.  b and c need not be equal.
+ *   u, ld_u   : fp32 (batch x a), row pitch ld_u >= a elements
+ *   packed_u  : the packed planes of u for the operand type (what rtk_pack_query_vectors gives for u), size
+ *               rtk_packed_query_bytes(dtype, batch, a); may be NULL; needs a <= 512
+ * Stage 2 is an existing entry point: z = rtk_score_packed_*(packed_u, batch, a, R, n_rel, ...) with the flags that call
+ * takes (fp32 with a % 4 != 0 runs on its v3 kernel), or rtk_score_f32(u, batch, a, R, n_rel, ...) for fp32 operands at
+ * any a.  With bf16 operands the planes hold u ROUNDED to bf16 (nearest even), as the query vectors v are on the
+ * 1-vs-all path; u itself stays fp32.
+ * Arithmetic: _f32 is the split-fp16 arithmetic of rtk_score_packed_f32's ws kernel (O[t_d] packed as a query row, the
+ * core's rows converted as entity rows, hi*hi + hi*lo + lo*hi per k-step, then acc * (row factor * column factor));
+ * _bf16 forms exact bf16 products in rtk_score_packed_bf16's chains (O[t_d] is copied into the planes, not rounded).
+ * S[h_d, j] enters as fp32; the b products of (d, i) are summed 32 at a time in a fixed tree and the ceil(b / 32) sums
+ * in ascending order.  The bits of u[d, :] depend only on O[t_d], S[h_d], the core and the operand type -- not on
+ * batch, on the query's place in it or on the other queries -- and repeated calls give the same bits (no atomics).
+ * Ids are range-checked on device: an id outside is clamped and raises the workspace's error word (1: subject id,
+ * 4: object id); the other rows of the batch are unaffected.
+ * Covered: _f32 c <= 208, c % 4 == 0, 16-byte-aligned core; _bf16 c <= 512; any a, b >= 1 with a * 32 ceil(b / 32)
+ * < 2^31 - 64; otherwise RTK_ERR_UNSUPPORTED ("c = .. above ..", "fp32 needs c % 4 == 0 and a 16-byte-aligned core").
+ * Null operands, batch < 0, a size < 1, ld_u < a: RTK_ERR_BAD_ARG.  A workspace that is missing, smaller than
+ * rtk_pair_vectors_workspace_bytes(dtype, batch, a, b, c) ("workspace of .. bytes given, .. needed") or not 256-byte
+ * aligned: RTK_ERR_WORKSPACE.  All of these are reported without touching a device.  batch == 0 is a no-op (the index
+ * vectors, u and the workspace may then be NULL).  The size query is valid without a device, 0 at batch <= 0 and for
+ * shapes that are not covered, and grows with batch.
+ */
+size_t rtk_pair_vectors_workspace_bytes(int dtype, int64_t batch, int a, int b, int c);
+int rtk_pair_vectors_f32(const float *core, int a, int b, int c, const float *S, int64_t n_subj, const float *O,
+                         int64_t n_obj, const int64_t *subject_idx, const int64_t *object_idx, int64_t batch, float *u,
+                         int64_t ld_u, void *packed_u, void *workspace, size_t ws_bytes, void *stream);
+int rtk_pair_vectors_bf16(const void *core, int a, int b, int c, const void *S, int64_t n_subj, const void *O,
+                          int64_t n_obj, const int64_t *subject_idx, const int64_t *object_idx, int64_t batch, float *u,
+                          int64_t ld_u, void *packed_u, void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

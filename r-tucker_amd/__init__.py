@@ -11,11 +11,12 @@ from .ops import (score_1vN, score_1vN_into, query_vectors, check_device_errors,
                   relation_tables, index_check, pack_query_vectors, score_packed_into, topk_1vN, rank_1vN,
                   score_candidates, score_triples, rank_targets_block, rank_counts_block_1vN, bce_loss_block_1vN,
                   topk_block_1vN, ce_loss_1vN, ce_partials_block_1vN, ce_merge_lse, ce_loss_block_1vN,
-                  rank_tie_counts_block_1vN, rank_ties_1vN, ranks_from_tie_counts)
+                  rank_tie_counts_block_1vN, rank_ties_1vN, ranks_from_tie_counts, pair_vectors, score_relations)
 from .sharded import EntityShards, ShardedEntityScorer  # noqa: F401
 from . import _lib  # noqa: F401
 from .evaluation import (DeviceFilter, evaluate, filtered_ranks, filtered_topk, metrics_from_ranks,  # noqa: F401
-                         filtered_tie_counts, tie_counts_block, metrics_from_tie_counts)
+                         filtered_tie_counts, tie_counts_block, metrics_from_tie_counts, RelationFilter, evaluate_relations,
+                         relation_tie_counts)
 from .model.asymmetric import R_TuckER as AsymmetricR_TuckER  # noqa: F401
 from .model.symmetric import R_TuckER as SymmetricR_TuckER  # noqa: F401
 from .riemannian import TuckerRiemannian, SFTuckerRiemannian, set_backend  # noqa: F401

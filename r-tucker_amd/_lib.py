@@ -118,6 +118,9 @@ SIGNATURES = {
     "rtk_ce_stream_rows_part_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, C.c_float, _p, _p, _p, _p, _sz, _p]),
     "rtk_ce_stream_grad_part_f32": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _p, _p, _p, _p,
                                           _p, _sz, _p]),
+    "rtk_pair_vectors_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
+    "rtk_pair_vectors_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
+    "rtk_pair_vectors_bf16": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
 }
 
 _lib = None

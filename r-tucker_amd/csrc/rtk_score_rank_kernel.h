@@ -251,6 +251,12 @@ struct SweepLane {
     int t, lane, wave, r, h;
 };
 
+// The row of O that row jl of the block reads: jl itself, unless the policy maps it (an optional hook, row_of(jl))
+template <typename P>
+__device__ __forceinline__ auto sweep_row(const P &pol, int jl, int) -> decltype(pol.row_of(jl)) { return pol.row_of(jl); }
+template <typename P>
+__device__ __forceinline__ int sweep_row(const P &, int jl, long) { return jl; }
+
 // The entity-stationary sweep.  Workgroup (slot, qs) of n_slots x qsplit takes the entity tiles slot, slot + n_slots,
 // ... of the block and the query tiles of range qs.  Each wave converts its 32 rows into B fragments ONCE per entity
 // tile, keeps them in registers and sweeps the query tiles, whose packed planes the workgroup stages through two LDS
@@ -270,6 +276,7 @@ struct SweepLane {
 //                          after that barrier; i is the tile's place in the range, `first` says that this is the
 //                          workgroup's first entity tile
 //   end_tile(ln, tile)     after the query loop
+//   row_of(jl)             optional: the row of O behind row jl of the block (default: jl; rtk_pair.hip pads its rows)
 template <typename T, int KS, int SG, typename P>
 __device__ __forceinline__ void sweep(P &pol, const unsigned char *__restrict__ qp, int B, const T *__restrict__ O,
                                       int n_local, int c, bool vec, int n_slots, int qsplit) {
@@ -312,7 +319,7 @@ __device__ __forceinline__ void sweep(P &pol, const unsigned char *__restrict__ 
         const int jl = tile * SW_TILE + wave * 32 + r;             // this lane's row of the block
         const bool valid = jl < n_local;
         Frag<T, KS> f;
-        f.load(O, min(jl, n_local - 1), c, h, vec);
+        f.load(O, sweep_row(pol, min(jl, n_local - 1), 0), c, h, vec);
         f.template convert<SG>();
         pol.begin_tile();
         if (tile == slot) {

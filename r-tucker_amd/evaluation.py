@@ -95,6 +95,82 @@ class DeviceFilter:
         return cache[device]
 
 
+class RelationFilter:
+    """The (subject, object) -> known-true-relations CSR of a ``KG_dataset`` on the device: the filter of relation
+    prediction, (h, ?, t).  It is built from the triples of the (subject, relation) -> objects lists the dataset holds
+    (all splits for a test-mode dataset) and has the fields of a ``DeviceFilter`` -- ``pair_ptr``, ``pair_obj`` (here:
+    relation ids, ascending and distinct within a list), ``slot_of_item``, ``features``, ``subj``, ``rel``, ``obj``,
+    ``max_list`` -- so ``filtered_ranks``, ``filtered_tie_counts``, ``filtered_topk`` and ``metrics_from_tie_counts`` take
+    it as they take a ``DeviceFilter``, with the (B, n_rel) matrix of ``score_relations`` as ``P`` and the relation id as
+    the target column."""
+
+    def __init__(self, dataset, device):
+        self.device = torch.device(device)
+        pairs = np.asarray(dataset._pairs, dtype=np.int64).reshape(-1, 2)
+        ptr, obj = np.asarray(dataset._ptr, dtype=np.int64), np.asarray(dataset._obj, dtype=np.int64)
+        sr = np.repeat(pairs, np.diff(ptr), axis=0)                        # (s, r) of every held triple
+        f = np.asarray(dataset.features, dtype=np.int64)
+        ne = int(max(dataset.n_ent, obj.max(initial=-1) + 1, 1))
+        nr = int(max(dataset.n_rel, sr[:, 1].max(initial=-1) + 1, 1))
+        self._key_ne = ne
+        # every (s, o, r) once, sorted by pair key then relation
+        key = np.unique((sr[:, 0] * ne + obj) * nr + sr[:, 1])
+        pk, rel = key // nr, key % nr
+        keys, counts = np.unique(pk, return_counts=True)                   # the pairs, by ascending key: slot = position
+        self.pair_ptr = torch.as_tensor(np.concatenate([[0], np.cumsum(counts)]).astype(np.int64), device=self.device)
+        self.pair_obj = torch.as_tensor(rel.astype(np.int64), device=self.device)
+        self.max_list = int(counts.max()) if len(counts) else 0
+        self._pair_keys = torch.as_tensor(keys.astype(np.int64), device=self.device)
+        if f.shape[1] > 2 and len(f):
+            ik = f[:, 0] * ne + f[:, 2]
+            pos = np.searchsorted(keys, ik)
+            if pos.max(initial=0) >= len(keys) or not np.array_equal(keys[np.minimum(pos, len(keys) - 1)], ik):
+                raise KeyError("an item's (subject, object) pair is not among the dataset's triples")
+            slots = pos.astype(np.int64)
+        else:                                                              # (train-mode items are (s, r) pairs: no slot)
+            slots = np.full(len(f), -1, dtype=np.int64)
+        self.slot_of_item = torch.as_tensor(slots, device=self.device)
+        self.features = torch.as_tensor(f, device=self.device)
+        self.subj = self.features[:, 0].contiguous()
+        self.rel = self.features[:, 1].contiguous()
+        self.obj = self.features[:, 2].contiguous() if f.shape[1] > 2 else None
+        self._plans = {}
+
+    def slots_of(self, subject_idx, object_idx) -> torch.Tensor:
+        """CSR slot (int64, on the filter's device) of arbitrary (subject, object) pairs, -1 for a pair no held triple
+        joins: a binary search of the sorted pair keys, no host loop and no host sync."""
+        h = torch.as_tensor(subject_idx).to(device=self.device, dtype=torch.int64).reshape(-1)
+        t = torch.as_tensor(object_idx).to(device=self.device, dtype=torch.int64).reshape(-1)
+        if h.numel() != t.numel():
+            raise RuntimeError(f"subject_idx has {h.numel()} entries, object_idx {t.numel()}")
+        keys = self._pair_keys
+        if keys.numel() == 0:
+            return torch.full_like(h, -1)
+        q = h * self._key_ne + t
+        pos = torch.searchsorted(keys, q).clamp_(max=keys.numel() - 1)
+        hit = (keys[pos] == q) & (h >= 0) & (t >= 0) & (t < self._key_ne)
+        return torch.where(hit, pos, torch.full_like(q, -1))
+
+    @classmethod
+    def of(cls, dataset, device):
+        """The relation filter of ``dataset`` on ``device``, built once per dataset object."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        cache = dataset.__dict__.setdefault("_relation_filters", {})
+        if device not in cache:
+            cache[device] = cls(dataset, device)
+        return cache[device]
+
+
+class _RowSlots:
+    """A filter's CSR with the rows' slots given directly (queries that are not dataset items): what the ``filtered_*``
+    calls read of a filter, with ``item_ids = arange(B)``."""
+
+    def __init__(self, flt, slots):
+        self.pair_ptr, self.pair_obj, self.slot_of_item = flt.pair_ptr, flt.pair_obj, slots
+
+
 def filtered_ranks(P: torch.Tensor, obj_idx: torch.Tensor, flt: DeviceFilter = None, item_ids: torch.Tensor = None,
                    want_bce: bool = False):
     """Ranks (int32, B) of ``obj_idx`` in the rows of ``P`` after filtering; optionally the per-row BCE sums."""
@@ -456,3 +532,60 @@ def _evaluate_generic(model, dataset, batch_size, device, flt, rank_type=None):
         return _tie_metrics(tie_sums, rank_type, n), acc[4] / n_batches
     sums = {"mrr": acc[0] / n, "hits@1": acc[1] / n, "hits@3": acc[2] / n, "hits@10": acc[3] / n}
     return sums, acc[4] / n_batches
+
+
+@torch.no_grad()
+def relation_tie_counts(P: torch.Tensor, relation_idx, flt=None, slots=None):
+    """``filtered_tie_counts`` on the (B, n_rel) matrix of ``score_relations`` for queries that are not dataset items:
+    ``slots`` = ``flt.slots_of(subject_idx, object_idx)`` of a ``RelationFilter`` (-1 = no list)."""
+    if flt is None:
+        return filtered_tie_counts(P, relation_idx)
+    ids = torch.arange(P.shape[0], device=P.device)
+    return filtered_tie_counts(P, relation_idx, _RowSlots(flt, slots), ids)
+
+
+@torch.no_grad()
+def evaluate_relations(model, dataset, batch_size=512, device=None, flt: RelationFilter = None, rank_type=None):
+    """``evaluate`` for relation prediction: every triple (h, r, t) of a test-mode ``dataset`` is the query (h, ?, t), r
+    is ranked among all relations after the other known relations of (h, t) are filtered out (``RelationFilter``).
+    Returns ``(metrics, None)``: the dictionary ``evaluate`` returns -- ``mrr``, ``hits@1``, ``hits@3``, ``hits@10``, plus
+    ``tied`` under a ``rank_type`` -- and None in the place of the loss, which this mode does not have.  Per batch:
+    ``ops.score_relations`` (no B x a*b intermediate), then the ranking kernels of the stored-matrix path on the
+    (B, n_rel) scores.  Out-of-range ids are reported at the pass's own synchronisation point."""
+    from . import ops
+    if rank_type is not None:
+        _check_tie_type(rank_type)
+    device = torch.device(device) if device is not None else next(model.parameters()).device
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    flt = flt or RelationFilter.of(dataset, device)
+    if flt.obj is None:
+        raise RuntimeError("evaluate_relations needs a test-mode dataset: its items are (subject, relation, object) triples")
+    model.eval()
+    sym = hasattr(model, "E")
+    core, R = model.core.data, model.R.weight.data
+    S = model.E.weight.data if sym else model.S.weight.data
+    O = S if sym else model.O.weight.data
+    n = len(dataset)
+    lib = _lib.load()
+    acc = torch.zeros(4, dtype=torch.float64, device=device)
+    tie_acc = torch.zeros(13, dtype=torch.float64, device=device) if rank_type is not None else None
+    with ops.index_check("deferred"):
+        for lo in range(0, n, batch_size):
+            hi = min(lo + batch_size, n)
+            ids = torch.arange(lo, hi, device=device)
+            P = ops.score_relations(core, R, S, O, flt.subj[lo:hi], flt.obj[lo:hi])
+            if rank_type is None:
+                m = metrics_from_ranks(filtered_ranks(P, flt.rel[lo:hi], flt, ids))
+                acc += torch.stack([m["mrr"], m["hits@1"].double(), m["hits@3"].double(), m["hits@10"].double()])
+            else:
+                greater, equal = filtered_tie_counts(P, flt.rel[lo:hi], flt, ids)
+                with torch.cuda.device(device):
+                    _lib.check(lib.rtk_tie_metrics_f64(greater.data_ptr(), equal.data_ptr(), hi - lo, tie_acc.data_ptr(),
+                                                       torch.cuda.current_stream(device).cuda_stream), "rtk_tie_metrics_f64")
+    sums = (acc if rank_type is None else tie_acc).cpu().tolist()
+    ops.check_device_errors(device)
+    if rank_type is not None:
+        return _tie_metrics(sums, rank_type, n), None
+    n = max(n, 1)
+    return {"mrr": sums[0] / n, "hits@1": sums[1] / n, "hits@3": sums[2] / n, "hits@10": sums[3] / n}, None

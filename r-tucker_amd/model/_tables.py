@@ -56,3 +56,45 @@ class TablesCacheMixin:
             self.__dict__["_tables"] = relation_tables(self.core.detach(), self.R.weight.detach())
             self.__dict__["_tables_key"] = key
         return self.__dict__["_tables"]
+
+
+class RelationQueriesMixin:
+    """Relation prediction, (h, ?, t), for both model flavours: the model's own parameters through
+    ``ops.score_relations`` (the symmetric model passes ``E`` as S and O)."""
+
+    def _relation_operands(self):
+        E = self.E.weight if hasattr(self, "E") else None
+        return self.core, self.R.weight, (E if E is not None else self.S.weight), (E if E is not None else self.O.weight)
+
+    @torch.no_grad()
+    def predict_relations(self, subject_idx, object_idx, k=10, flt=None):
+        """The ``k`` most likely relations of each ``(subject, ?, object)`` query, best first: ``(values, ids)``
+        (``ops.score_relations``, then ``evaluation.filtered_topk`` on the (B, n_rel) scores; ``flt``: a
+        ``RelationFilter`` whose known-true relations are left out).  What the selection refuses (a ``k`` it does not
+        take) is its own error."""
+        from ..evaluation import filtered_topk
+        from ..ops import score_relations
+        P = score_relations(*self._relation_operands(), subject_idx, object_idx)
+        if flt is None:
+            return filtered_topk(P, k)
+        return filtered_topk(P, k, flt, slots=flt.slots_of(subject_idx, object_idx))
+
+    @torch.no_grad()
+    def rank_relations(self, subject_idx, relation_idx, object_idx, flt=None, rank_type=None):
+        """Filtered rank (B,) of ``relation_idx`` among all relations for each ``(subject, ?, object)`` query (``flt``: a
+        ``RelationFilter``; the other known relations of the pair are set to 0).  ``rank_type``: None = the stable rule
+        (int32, ``filtered_ranks``), or "optimistic" / "realistic" / "pessimistic" from the two tie counts
+        (``ops.ranks_from_tie_counts``)."""
+        from ..evaluation import _RowSlots, _check_tie_type, filtered_ranks, relation_tie_counts
+        from ..ops import ranks_from_tie_counts, score_relations
+        if rank_type is not None:
+            _check_tie_type(rank_type)
+        P = score_relations(*self._relation_operands(), subject_idx, object_idx)
+        rel = torch.as_tensor(relation_idx).to(device=P.device, dtype=torch.int64).reshape(-1)
+        slots = flt.slots_of(subject_idx, object_idx) if flt is not None else None
+        if rank_type is None:
+            if flt is None:
+                return filtered_ranks(P, rel)
+            return filtered_ranks(P, rel, _RowSlots(flt, slots), torch.arange(P.shape[0], device=P.device))
+        greater, equal = relation_tie_counts(P, rel, flt, slots)
+        return ranks_from_tie_counts(greater, equal, rank_type)

@@ -13,10 +13,10 @@ import torch
 from torch import nn
 
 from ...ops import rank_1vN, score_1vN, score_candidates, score_triples, topk_1vN
-from .._tables import TablesCacheMixin
+from .._tables import RelationQueriesMixin, TablesCacheMixin
 
 
-class R_TuckER(TablesCacheMixin, nn.Module):
+class R_TuckER(TablesCacheMixin, RelationQueriesMixin, nn.Module):
     def __init__(self, data_count, rank=None, **kwargs):
         super().__init__()
         n_ent, n_rel = data_count

@@ -91,7 +91,7 @@ def _entry(name, bf16):
 
 
 class _Operands:
-    """The checked operands of one call: core (a, b, c), R and, when given, S, O and the index vectors h, r of B queries;
+    """The checked operands of one call: core (a, b, c) and, when given, R, S, O and the index vectors h, r of B queries;
     contiguous, on one GPU, in one dtype, with matching widths (the C ABI takes a, b, c from the core alone)."""
     __slots__ = ("core", "R", "S", "O", "h", "r", "a", "b", "c", "B", "dev", "bf16", "dcode")
 
@@ -103,17 +103,17 @@ class _Operands:
         self.bf16 = dt == torch.bfloat16
         self.dcode = _dtype_code(self.bf16)
         self.core = core = core.contiguous()
-        self.R = R = _operand("R", R, dt)
+        self.R = R = None if R is None else _operand("R", R, dt)
         self.S = S = None if S is None else _operand("S", S, dt)
         self.O = O = None if O is None else _operand("O", O, dt)
         self.dev = dev = core.device
         for n, t in (("R", R), ("S", S), ("O", O)):
             if t is not None and t.device != dev:
                 raise RuntimeError(f"{n} is on {t.device}, core on {dev}")
-        if core.dim() != 3 or R.dim() != 2 or (S is not None and S.dim() != 2) or (O is not None and O.dim() != 2):
+        if core.dim() != 3 or any(t is not None and t.dim() != 2 for t in (R, S, O)):
             raise RuntimeError("expected core (a,b,c), R (nR,a), S (N,b), O (N,c)")
         self.a, self.b, self.c = a, b, c = core.shape
-        if R.shape[1] != a or (S is not None and S.shape[1] != b) or (O is not None and O.shape[1] != c):
+        if (R is not None and R.shape[1] != a) or (S is not None and S.shape[1] != b) or (O is not None and O.shape[1] != c):
             raise RuntimeError("factor widths " + ", ".join(f"{n} {t.shape[1]}" for n, t in (("R", R), ("S", S), ("O", O))
                                                             if t is not None) + f" do not match core {tuple(core.shape)}")
         self.h = self.r = None
@@ -1710,6 +1710,68 @@ def score_triples(core, R, S, O, subject_idx, relation_idx, object_idx, sigmoid=
         t = torch.as_tensor(t)
     return score_candidates(core, R, S, O, subject_idx, relation_idx, t.reshape(-1, 1), sigmoid=sigmoid,
                             sigmoid_mode=sigmoid_mode, tables=tables).view(-1)
+
+
+def _pair_stage1(op, h, t, B, sp, u, qp):
+    """``rtk_pair_vectors_*``: ``u`` (B, a) fp32 and, when ``qp`` is given, its packed planes.  Returns the workspace."""
+    ws = _workspace(op.dev, sp, _size("rtk_pair_vectors_workspace_bytes", op.dcode, B, op.a, op.b, op.c))
+    _lib.check(_entry("rtk_pair_vectors", op.bf16)(
+        op.core.data_ptr(), op.a, op.b, op.c, op.S.data_ptr(), op.S.shape[0], op.O.data_ptr(), op.O.shape[0],
+        h.data_ptr(), t.data_ptr(), B, u.data_ptr(), op.a, None if qp is None else qp.data_ptr(), ws.data_ptr(), ws.numel(),
+        sp), "rtk_pair_vectors")
+    return ws
+
+
+def _pair_queries(op, subject_idx, object_idx):
+    h, t = _idx("subject_idx", subject_idx, op.dev), _idx("object_idx", object_idx, op.dev)
+    if h.numel() != t.numel():
+        raise RuntimeError(f"subject_idx has {h.numel()} entries, object_idx {t.numel()}")
+    return h, t, h.numel()
+
+
+@torch.no_grad()
+def pair_vectors(core, S, O, subject_idx, object_idx, packed=False):
+    """Stage 1 of relation prediction: ``u[d, i] = sum_jk G[i, j, k] S[h_d, j] O[t_d, k]`` -> ``(B, a)`` fp32
+    (``rtk_pair_vectors_*``; symmetric model: pass ``S is O``).  ``packed=True`` returns ``(u, planes)`` with the packed
+    planes of ``u`` (``pack_query_vectors(u, core.dtype)``'s bytes), which a score kernel takes against ``R``.  Nothing
+    of size B x a*b is written.  The bits of a row depend only on ``O[t_d]``, ``S[h_d]``, the core and the dtype, not on
+    the batch.  Inference only: runs under ``torch.no_grad()``, no autograd.  An id outside its table is clamped and
+    raises ``IndexError`` by the ``index_check`` policy."""
+    op = _Operands(core, None, S, O)
+    h, t, B = _pair_queries(op, subject_idx, object_idx)
+    u = torch.empty((B, op.a), dtype=torch.float32, device=op.dev)
+    qp = torch.empty(_size("rtk_packed_query_bytes", op.dcode, B, op.a), dtype=torch.uint8, device=op.dev) if packed else None
+    if B > 0:
+        with torch.cuda.device(op.dev):
+            sp = _stream_ptr(op.dev)
+            _strict_check(_pair_stage1(op, h, t, B, sp, u, qp), sp)
+    return (u, qp) if packed else u
+
+
+@torch.no_grad()
+def score_relations(core, R, S, O, subject_idx, object_idx, sigmoid=True, sigmoid_mode=None):
+    """Scores of every relation for a batch of (h, ?, t) queries -> ``(B, n_rel)`` fp32: ``logistic(u_d . R[r])`` with the
+    pair vectors ``u`` of ``pair_vectors``; column r is the 1-vs-all score of ``(h_d, r)`` at entity ``t_d``.  Stage 2 is
+    the score kernel of the 1-vs-all path on the packed planes of ``u`` against ``R`` (bf16 operands: ``u`` is rounded to
+    bf16 there, as the query vectors are); fp32 operands with a relation rank above 512 go through ``rtk_score_f32``.
+    ``sigmoid_mode`` as for ``score_1vN``.  Inference only: runs under ``torch.no_grad()``, no autograd."""
+    op = _Operands(core, R, S, O)
+    h, t, B = _pair_queries(op, subject_idx, object_idx)
+    flags = _score_flags(sigmoid, sigmoid_mode, torch.float32, op.bf16)
+    out = torch.empty((B, op.R.shape[0]), dtype=torch.float32, device=op.dev)
+    if B == 0:
+        return out
+    packed = _packed_stage2(op.a, exact=False)
+    if op.bf16 and not packed:
+        raise RuntimeError(f"bf16 operands: only the bf16 MFMA score kernel exists (relation rank a <= {_PACKED_MAX_C})")
+    with torch.cuda.device(op.dev):
+        sp = _stream_ptr(op.dev)
+        u = torch.empty((B, op.a), dtype=torch.float32, device=op.dev)
+        qp = _packed_buffer(op.dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.a)) if packed else None
+        ws = _pair_stage1(op, h, t, B, sp, u, qp)
+        _stage2(op.bf16, sp, u, qp, op.R, out, flags)
+        _strict_check(ws, sp)
+    return out
 
 
 def cg_fifth_group_columns(N, c, flags=0):
