@@ -297,7 +297,13 @@ int rtk_gemm_f32_splitk(const float *A, int a_kmajor, int64_t lda,
  * scaled by the power of two that puts its bound just below 2^15, so an element larger than the bound
  * overflows to inf (loud), and an element keeps max(2^-22 |x|, 2^-40 bound) of absolute accuracy: the
  * result is accurate normwise, relative to max|A| max|B| K -- right for a gradient, not for an
- * orthogonalisation (use rtk_gemm_f32 there).  splits == 1: C may have any ldc >= N, no workspace;
+ * orthogonalisation (use rtk_gemm_f32 there).  The power of two is 2^e, e = 14 - floor(log2 bound), taken from the
+ * bound's exponent field: every normal bound up to FLT_MAX is served (e >= -113), e is capped at 100, so an operand
+ * under a bound below 2^-86 is scaled by 2^100 all the same and loses bits to fp16's subnormals; a bound that is 0,
+ * subnormal, inf or nan gets the scale 1 -- a subnormal operand then contributes zeros, and an operand under an inf
+ * or nan bound is taken as it stands and has to lie within fp16's range itself.  The accumulator is multiplied by
+ * 2^-(ea + eb) in one step where that is a normal float, else in two steps of the same sign: the result is the
+ * rounded one whenever it is a normal float, whatever the two bounds are.  splits == 1: C may have any ldc >= N, no workspace;
  * splits > 1: as rtk_gemm_f32_splitk (slabs added in chunk order: deterministic). */
 int rtk_gemm_sf16_splitk(const float *A, int a_kmajor, int64_t lda, const float *amax_a,
                          const float *B, int b_kmajor, int64_t ldb, const float *amax_b,

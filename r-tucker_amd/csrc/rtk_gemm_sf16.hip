@@ -109,12 +109,18 @@ __device__ __forceinline__ void stash_fragment(const Stage16 &s, int half, f16x8
     lds[frag_index(plane_hi + 1, ks, hh, row)] = lo;
 }
 
-// 2^e with max|x| * 2^e in [2^14, 2^15) for the bound `amax` (0, inf or nan -> 1: nothing to scale / nothing to save)
+// 2^e with max|x| * 2^e in [2^14, 2^15) for the bound `amax` (0, subnormal, inf or nan -> 1: nothing to scale /
+// nothing to save; a subnormal operand times 1 has zero hi and lo planes).  e <= 100 keeps 2^e a normal fp32 (a bound
+// below 2^-86 is scaled by 2^100 all the same and loses bits to fp16's subnormals); downwards the exponent field
+// itself ends at e = 14 - 127 = -113, where 2^e and 2^-e are normals still: nothing is clamped there (under the
+// former clamp at -100 an element within a bound of 2^116 and more left fp16's range).  The max(-113, .) below changes
+// no value; without it this toolchain allocates the main loop's registers differently (13 spilled VGPRs in place of 4
+// in the M-major kernel: dO at c = 200 took 74 us in place of 67).
 __device__ __forceinline__ float operand_scale(float amax, int &e) {
     const unsigned bits = __builtin_bit_cast(unsigned, amax) & 0x7fffffffu;
     const int ex = (int)(bits >> 23);             // biased exponent; 0 = zero / subnormal
     e = (ex == 0 || ex == 255) ? 0 : 14 - (ex - 127);
-    e = max(-100, min(100, e));
+    e = max(-113, min(100, e));
     return __builtin_bit_cast(float, (unsigned)(127 + e) << 23);
 }
 
@@ -142,10 +148,6 @@ __global__ __launch_bounds__(256, 2) void gemm_sf16_kernel(
 
     int ea, eb;
     const float sa = operand_scale(*amax_a, ea), sb = operand_scale(*amax_b, eb);
-    // 2^-(ea+eb) in two factors: each is a normal fp32 for |e| <= 100
-    const float ua = __builtin_bit_cast(float, (unsigned)(127 - ea) << 23);
-    const float ub = __builtin_bit_cast(float, (unsigned)(127 - eb) << 23);
-
     f32x16 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -254,6 +256,13 @@ __global__ __launch_bounds__(256, 2) void gemm_sf16_kernel(
     }
     }
 #undef RTK_SF16_STEP
+
+    // 2^s, s = -(ea + eb) in [-200, 226]: ONE factor whenever it is a normal fp32, else two normals of the same sign --
+    // neither multiplication then over- or underflows unless the result itself does (2^-ea first and 2^-eb second
+    // overflowed in between for a bound of 2^110 against one of 2^-60)
+    const int us = -(ea + eb), us1 = max(-126, min(127, us));
+    const float ua = __builtin_bit_cast(float, (unsigned)(127 + us1) << 23);
+    const float ub = __builtin_bit_cast(float, (unsigned)(127 + us - us1) << 23);
 
     // C/D map of the 32x32 MFMA: column = lane & 31, row = (e & 3) + 8*(e >> 2) + 4*(lane >> 5)
 #pragma unroll
