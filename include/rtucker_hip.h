@@ -784,7 +784,24 @@ int rtk_score_topk_bf16(const void *q_packed, int64_t batch, int c, const void *
  * of the next MFMA: in sweep 1 (rows) the query is on the lane and the tile is the A operand of X O, in sweep 2
  * (grad_o) the entity is on the lane and the tile is the A operand of X^T V.  Both products are three f16 MFMAs per
  * k-step on hi/lo halves with fp32 accumulation (x scaled by 2^14; O and scale * v by the power of two that brings
- * their largest magnitude into [2^14, 2^15)): the accuracy class of rtk_gemm_sf16_splitk.
+ * their largest magnitude into [2^14, 2^15)).
+ * Accuracy, per element against float64 of the fp32 operands (u = 2^-24, u22 = 2^-22; derivation and tests:
+ * tests/golden/bce_stream_cases.py, tests/test_gpu_bce_stream_kernels.py).  A logit carries the split chain's error
+ * dz <= (3 + 0.75 ceil(c / 16)) u22 sum_k |v_k| |O_jk|; its probability dp <= 1.01 p (1 - p) (darg + dz) + k u p with
+ * darg = (2.25 |z| + 2) u, k = 3 (fast logistic) or (2.25 |z| + 6) u, k = 2 (exact): the roundings of 1 + e and of the
+ * reciprocal are absolute errors of a number near 1, so ln(1 - p), formed from the fp32 p, is off by up to
+ * -ln(1 - dp / (1 - p)) -- relative to 1 - p, not to p (at z = 15, 1 - p = 3.1e-7 and dp = 1.8e-7): the conditioning of
+ * BCE on fp32 probabilities.  Saturated elements (p exactly 1.0f from z = 16.64 on, 0.0f below z = -88.7; between -89.5
+ * and -86.5 the two logistics differ) are exact: x = 0 and the logs 0 and -100.
+ *   loss_rows  per element t0 Lp + (1 - t0) Lq, Lp = -ln(1 - dp / p), Lq = -ln(1 - (dp + u (1 - p)) / (1 - p)), plus
+ *              24 u of |t0 ln p| + |(1 - t0) ln(1 - p)| (rtk_clog at 4 u, the products, sixteen fp32 adds per lane and
+ *              tile), float64 from there; a CSR entry adds (1 - eps) (Lp + Lq) and (ceil(n_d / 128) + 16) u of its |terms|.
+ *   dv         sum_j (dp_j + u |x_j|) |O_jk| + (3 u22 + r_j u) sum_j |x_j| |O_jk| + 2^-39 (sum_j |O_jk| + max|O| sum_j |x_j|)
+ *              + (32 ceil(n_d / 128) + 6) u (1 - eps) sum_t |O_tk| + 2 u |dv|, r_j <= 3 (16-row groups left in the split)
+ *              + (splits left) + 2 the fp32 roundings a term passes; a query without an unsaturated element: zero bits.
+ *   gO         the same with scale v for O (3 u22 + u: scale * v is rounded), the query groups for the entity groups
+ *              and (m_j + 6) u for the m_j CSR entries the ordered scatter adds into row j; an entity that no
+ *              unsaturated element touches: +0.0.
  * Summation orders (no float atomics; repeated calls give the same bits):
  *   rows:   a workgroup holds 128 queries and walks a contiguous range of 32-row entity tiles in increasing order; the
  *           entity tiles are cut into `splits` = max(1, 256 / ceil(batch / 128)) ranges -- a function of batch and the
@@ -831,7 +848,9 @@ int rtk_bce_stream_grad_o_f32(const void *q_packed, const float *v, int64_t batc
  *                                   forward, batch x c floats in the backward, before rtk_query_vectors_bwd_f32).
  *   rtk_bce_stream_grad_o_part_f32  gO_local_out (n_local x c) = the block's rows of gO, written in full; no exchange.
  * Summed (rows, dv) or concatenated (gO) over any partition of [0, n_ent) into blocks they are the outputs of
- * rtk_bce_stream_rows_f32 / rtk_bce_stream_grad_o_f32 on the whole matrix up to the order of the fp32 / fp64 sums;
+ * rtk_bce_stream_rows_f32 / rtk_bce_stream_grad_o_f32 on the whole matrix up to the order of the fp32 / fp64 sums
+ * (per element within TWICE the whole-matrix bounds stated there: the fp32 sums run per block and then over the blocks,
+ * and the power of two of O in the dv product is the block's own);
  * with col0 = 0 and n_local = n_ent they have those calls' bits (the whole-matrix entry points ARE this block).
  * The smoothing term is eps / n_ent, the GLOBAL entity count, and the caller's scale is g / (batch n_ent).  A CSR
  * entry e belongs to the block iff col0 <= e < col0 + n_local (local row e - col0); the others are skipped in the loss
