@@ -1039,6 +1039,55 @@ int rtk_pair_vectors_bf16(const void *core, int a, int b, int c, const void *S, 
                           int64_t n_obj, const int64_t *subject_idx, const int64_t *object_idx, int64_t batch, float *u,
                           int64_t ld_u, void *packed_u, void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * Training relation prediction: the gradients of z[d, r] above (csrc/rtk_pair_bwd.hip).  Given dZ (batch x n_rel),
+ *     du = dZ . R,   gR = dZ^T . u                          rtk_gemm_f32
+ *     rS[d, j] = sum_i du[d, i] * sum_k G[i, j, k] O[t_d, k]     gS[e, :] = sum_{d: h_d = e} rS[d, :]
+ *     rO[d, k] = sum_i du[d, i] * sum_j G[i, j, k] S[h_d, j]     gO[e, :] = sum_{d: t_d = e} rO[d, :]
+ *     gG[i, j, k] = sum_d du[d, i] S[h_d, j] O[t_d, k]
+ * Nothing of size batch x a*b is written.  fp32 only.
+ *
+ * rtk_pair_rows_f32:
+ *     rows[d, j] = sum_i w[d, i] * sum_k core[i, j, k] X[x_idx[d], k]        (batch x b) fp32, row pitch ld_rows >= b
+ * rS is this call on (core, O, t, du); rO is this call on the core with its last two axes transposed and (S, h, du).
+ * It is rtk_pair_vectors_f32's sweep with i and j exchanged: the rows of the sweep are j * a_pad + i, a_pad =
+ * 32 ceil(a / 32), a 32 x 32 tile of sum_k core[i, j, k] X[x_d, k] (the split-fp16 arithmetic of rtk_pair_vectors_f32)
+ * is multiplied by w[d, i] (fp32, row pitch ld_w >= a) in registers, the a products of (d, j) are summed 32 at a time in
+ * a fixed tree and the ceil(a / 32) sums in ascending order; only batch * b * ceil(a / 32) partial sums reach the
+ * workspace.  The bits of rows[d, :] depend only on X[x_idx[d]], w[d, :] and the core; repeated calls give the same bits
+ * (no atomics).  An id outside [0, n_x) is clamped and raises the workspace's error word (4); the other rows are
+ * unaffected.  Covered shapes, refusals, return codes and messages as rtk_pair_vectors_f32: c <= 208, c % 4 == 0 and a
+ * 16-byte-aligned core, b * 32 ceil(a / 32) < 2^31 - 64 ("dimension too large"): RTK_ERR_UNSUPPORTED; null operands,
+ * batch < 0, a size < 1, ld_w < a, ld_rows < b: RTK_ERR_BAD_ARG; a workspace that is missing, smaller than
+ * rtk_pair_rows_workspace_bytes(batch, a, b, c) or not 256-byte aligned: RTK_ERR_WORKSPACE.  batch == 0 is a no-op
+ * after the shape checks.  The size query is valid without a device and 0 at batch <= 0 or a shape not covered.
+ *
+ * rtk_core_outer_f32:
+ *     gG[i, j, k] = sum_d (x[d, i] * y[d, j]) * z[d, k]        (a, b, c) fp32, dense
+ * by v_mfma_f32_32x32x2_f32.  The left operand element is the single fp32 product x[d, i] * y[d, j], formed while it is
+ * staged and never written to memory.  ONE accumulation chain per output element, over d ascending from zero in k-tiles
+ * of 16 (the last zero-padded), no split-K: the bits are those of rtk_gemm_f32 on the materialised X[d, i b + j] =
+ * x[d, i] * y[d, j] (M-major X, lda = a*b; M-major z; M = a*b, N = c, K = batch).  batch == 0 zeroes gG.  Null operands,
+ * a size < 1, batch < 0, a pitch below its width: RTK_ERR_BAD_ARG; a*b*c or batch outside 31 bits: RTK_ERR_UNSUPPORTED.
+ *
+ * rtk_scatter_rows_f32:
+ *     out[e, :] = sum_{d: idx[d] = e} rows[d, :]        (n_out x n) fp32 dense; rows nobody names are zero
+ * The ordered scatter with entity idx[d], owner d and factor 1, cut into windows of 256 sorted entries whatever the
+ * batch: within an entity the rows are added in increasing d, each window's run from 0, a run over several windows as
+ * the sum of the windows' partial sums in window order.  No float atomics.  Ids outside [0, n_out) add nothing.
+ * n <= 1024 (RTK_ERR_UNSUPPORTED above), ld_rows >= n; workspace of rtk_scatter_rows_workspace_bytes(batch), 256-byte
+ * aligned (RTK_ERR_WORKSPACE).  batch == 0 zeroes out.
+ */
+size_t rtk_pair_rows_workspace_bytes(int64_t batch, int a, int b, int c);
+int rtk_pair_rows_f32(const float *core, int a, int b, int c, const float *X, int64_t n_x, const int64_t *x_idx,
+                      const float *w, int64_t ld_w, int64_t batch, float *rows, int64_t ld_rows, void *workspace,
+                      size_t ws_bytes, void *stream);
+int rtk_core_outer_f32(const float *x, int64_t ld_x, int a, const float *y, int64_t ld_y, int b, const float *z,
+                       int64_t ld_z, int c, int64_t batch, float *gG, void *stream);
+size_t rtk_scatter_rows_workspace_bytes(int64_t batch);
+int rtk_scatter_rows_f32(const int64_t *idx, const float *rows, int64_t ld_rows, int64_t batch, int n, int64_t n_out,
+                         float *out, void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

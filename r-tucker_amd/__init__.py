@@ -11,7 +11,8 @@ from .ops import (score_1vN, score_1vN_into, query_vectors, check_device_errors,
                   relation_tables, index_check, pack_query_vectors, score_packed_into, topk_1vN, rank_1vN,
                   score_candidates, score_triples, rank_targets_block, rank_counts_block_1vN, bce_loss_block_1vN,
                   topk_block_1vN, ce_loss_1vN, ce_partials_block_1vN, ce_merge_lse, ce_loss_block_1vN,
-                  rank_tie_counts_block_1vN, rank_ties_1vN, ranks_from_tie_counts, pair_vectors, score_relations)
+                  rank_tie_counts_block_1vN, rank_ties_1vN, ranks_from_tie_counts, pair_vectors, score_relations,
+                  relation_logits, relation_ce_loss, pair_rows, core_outer, scatter_rows)
 from .sharded import EntityShards, ShardedEntityScorer  # noqa: F401
 from . import _lib  # noqa: F401
 from .evaluation import (DeviceFilter, evaluate, filtered_ranks, filtered_topk, metrics_from_ranks,  # noqa: F401

@@ -121,6 +121,11 @@ SIGNATURES = {
     "rtk_pair_vectors_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),
     "rtk_pair_vectors_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
     "rtk_pair_vectors_bf16": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _i64, _p, _p, _sz, _p]),
+    "rtk_pair_rows_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rtk_pair_rows_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _p, _i64, _i64, _p, _i64, _p, _sz, _p]),
+    "rtk_core_outer_f32": (_i, [_p, _i64, _i, _p, _i64, _i, _p, _i64, _i, _i64, _p, _p]),
+    "rtk_scatter_rows_workspace_bytes": (_sz, [_i64]),
+    "rtk_scatter_rows_f32": (_i, [_p, _p, _i64, _i64, _i, _i64, _p, _p, _sz, _p]),
 }
 
 _lib = None

@@ -38,3 +38,7 @@ int rtk_scatter_candidates(const char *fn, const int64_t *cand, int64_t ld_cand,
 // Flat lists: entry i < m has entity ent[i], query owner[i] and dz[i].
 int rtk_scatter_flat(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m, int64_t n_ent,
                      const float *v, int c, float *gO, void *workspace, hipStream_t st);
+
+// The same with a row pitch on v: query d's row starts at v + d ld_v (ld_v >= c).  The sums are those of ld_v == c.
+int rtk_scatter_flat_ld(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m, int64_t n_ent,
+                        const float *v, int64_t ld_v, int c, float *gO, void *workspace, hipStream_t st);

@@ -175,8 +175,8 @@ __device__ __forceinline__ void store_row(float *__restrict__ dst, const float (
 template <int NCH, bool VEC>
 __global__ __launch_bounds__(256) void run_sum_kernel(const int32_t *__restrict__ skey, const int32_t *__restrict__ sval,
                                                      int64_t M, int64_t n_ent, const float *__restrict__ dz,
-                                                     int64_t ld_dz, int64_t K, const float *__restrict__ v, int c,
-                                                     float *__restrict__ gO, float *__restrict__ P, int64_t win,
+                                                     int64_t ld_dz, int64_t K, const float *__restrict__ v, int64_t ld_v,
+                                                     int c, float *__restrict__ gO, float *__restrict__ P, int64_t win,
                                                      const int32_t *__restrict__ owner) {
     constexpr int U = NCH <= 2 ? 8 : 4;
     const int lane = threadIdx.x & 63;
@@ -222,7 +222,7 @@ __global__ __launch_bounds__(256) void run_sum_kernel(const int32_t *__restrict_
         for (int u = 0; u < U; ++u) {
             const int64_t vr = owner ? (int64_t)owner[dd[u]] : dd[u];      // flat list (K = 1): entry -> its query
 #pragma unroll
-            for (int i = 0; i < NCH; ++i) x[u][i] = rtk_load_piece<float, VEC>(v + vr * c, i * 256 + lane * 4, c);
+            for (int i = 0; i < NCH; ++i) x[u][i] = rtk_load_piece<float, VEC>(v + vr * ld_v, i * 256 + lane * 4, c);
         }
 #pragma unroll
         for (int u = 0; u < U; ++u) {
@@ -312,9 +312,9 @@ ScatterPlan carve(void *base, int64_t M, int64_t win) {
 unsigned key_blocks(int64_t M) { return (unsigned)(rtk_cdiv(M, 256) < 4096 ? rtk_cdiv(M, 256) : 4096); }
 
 // The keys / vals of ws.keys[0], ws.vals[0] sorted by entity (stable), then the ordered sums into gO (zeroed by the caller).
-// `owner` (flat lists, k = 1): entry i belongs to query owner[i]; null: to query i / k.
+// `owner` (flat lists, k = 1): entry i belongs to query owner[i]; null: to query i / k.  `ld_v`: the row pitch of v.
 int sorted_scatter(const char *fn, const ScatterPlan &ws, int64_t n_ent, const float *dz, int64_t ld_dz, int64_t k,
-                   const int32_t *owner, const float *v, int c, float *gO, hipStream_t st) {
+                   const int32_t *owner, const float *v, int64_t ld_v, int c, float *gO, hipStream_t st) {
     const int64_t M = ws.M;
     int bits = 1;
     while ((n_ent >> bits) != 0) ++bits;             // keys are <= n_ent
@@ -328,13 +328,13 @@ int sorted_scatter(const char *fn, const ScatterPlan &ws, int64_t n_ent, const f
         hipLaunchKernelGGL(sort_place_kernel, dim3(tblocks), dim3(256), 0, st, ws.keys[src], ws.vals[src], M, shift,
                            ws.ntiles, ws.offs, ws.keys[src ^ 1], ws.vals[src ^ 1]);
     }
-    const bool vec = c % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(gO)) & 15) == 0;
+    const bool vec = c % 4 == 0 && ld_v % 4 == 0 && ((reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(gO)) & 15) == 0;
     const unsigned wblocks = (unsigned)rtk_cdiv(ws.nwin, SC_WAVES);
     auto go = [&](auto nc, auto vc) {
         constexpr int NC = decltype(nc)::value;
         constexpr bool VC = decltype(vc)::value;
         RTK_LAUNCH_SCORE((run_sum_kernel<NC, VC>), dim3(wblocks), dim3(256), 0, st, ws.keys[src], ws.vals[src], M, n_ent,
-                         dz, ld_dz, k, v, c, gO, ws.P, ws.win, owner);
+                         dz, ld_dz, k, v, ld_v, c, gO, ws.P, ws.win, owner);
         hipLaunchKernelGGL((run_combine_kernel<NC, VC>), dim3(wblocks), dim3(256), 0, st, ws.keys[src], M, n_ent, c, gO,
                            ws.P, ws.win);
     };
@@ -352,16 +352,21 @@ int rtk_scatter_candidates(const char *fn, const int64_t *cand, int64_t ld_cand,
     if (rc != RTK_OK || M <= 0) return rc;
     const ScatterPlan ws = carve(workspace, M, rtk_scatter_window(M));
     hipLaunchKernelGGL(cand_keys_kernel, dim3(key_blocks(M)), dim3(256), 0, st, cand, ld_cand, k, n_ent, M, ws.keys[0], ws.vals[0]);
-    return sorted_scatter(fn, ws, n_ent, dz, ld_dz, k, nullptr, v, c, gO, st);
+    return sorted_scatter(fn, ws, n_ent, dz, ld_dz, k, nullptr, v, c, c, gO, st);
 }
 
-int rtk_scatter_flat(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m, int64_t n_ent,
-                     const float *v, int c, float *gO, void *workspace, hipStream_t st) {
+int rtk_scatter_flat_ld(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m, int64_t n_ent,
+                        const float *v, int64_t ld_v, int c, float *gO, void *workspace, hipStream_t st) {
     const int rc = rtk_zero_async(fn, gO, (size_t)n_ent * c * 4, st);
     if (rc != RTK_OK || m <= 0) return rc;
     // m is the caller's BOUND on the entries (the surplus slots sort last and add nothing): the sums must not depend on
     // it, so the flat lists are always cut into the longest window, which P -- carved for rtk_scatter_window(m) -- holds
     const ScatterPlan ws = carve(workspace, m, RTK_SCATTER_WIN_MAX);
     hipLaunchKernelGGL(flat_keys_kernel, dim3(key_blocks(m)), dim3(256), 0, st, ent, n_ent, m, ws.keys[0], ws.vals[0]);
-    return sorted_scatter(fn, ws, n_ent, dz, 1, 1, owner, v, c, gO, st);
+    return sorted_scatter(fn, ws, n_ent, dz, 1, 1, owner, v, ld_v, c, gO, st);
+}
+
+int rtk_scatter_flat(const char *fn, const int32_t *ent, const int32_t *owner, const float *dz, int64_t m, int64_t n_ent,
+                     const float *v, int c, float *gO, void *workspace, hipStream_t st) {
+    return rtk_scatter_flat_ld(fn, ent, owner, dz, m, n_ent, v, c, c, gO, workspace, st);
 }

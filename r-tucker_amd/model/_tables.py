@@ -66,6 +66,13 @@ class RelationQueriesMixin:
         E = self.E.weight if hasattr(self, "E") else None
         return self.core, self.R.weight, (E if E is not None else self.S.weight), (E if E is not None else self.O.weight)
 
+    def relation_logits(self, subject_idx, object_idx):
+        """Logits ``(B, n_rel)`` of every relation for each ``(subject, ?, object)`` query, differentiable in the model's
+        parameters (``ops.relation_logits``; the cached relation tables are not used): the input of a
+        relation-classification loss such as ``ops.relation_ce_loss``."""
+        from ..ops import relation_logits
+        return relation_logits(*self._relation_operands(), subject_idx, object_idx)
+
     @torch.no_grad()
     def predict_relations(self, subject_idx, object_idx, k=10, flt=None):
         """The ``k`` most likely relations of each ``(subject, ?, object)`` query, best first: ``(values, ids)``

@@ -1757,21 +1757,174 @@ def score_relations(core, R, S, O, subject_idx, object_idx, sigmoid=True, sigmoi
     ``sigmoid_mode`` as for ``score_1vN``.  Inference only: runs under ``torch.no_grad()``, no autograd."""
     op = _Operands(core, R, S, O)
     h, t, B = _pair_queries(op, subject_idx, object_idx)
-    flags = _score_flags(sigmoid, sigmoid_mode, torch.float32, op.bf16)
+    return _relation_forward(op, h, t, B, _score_flags(sigmoid, sigmoid_mode, torch.float32, op.bf16))[0]
+
+
+def _relation_forward(op, h, t, B, flags):
+    """``(scores (B, n_rel) fp32, u (B, a) fp32)`` of ``score_relations``: ``rtk_pair_vectors_*``, then stage 2 on ``R``."""
     out = torch.empty((B, op.R.shape[0]), dtype=torch.float32, device=op.dev)
+    u = torch.empty((B, op.a), dtype=torch.float32, device=op.dev)
     if B == 0:
-        return out
+        return out, u
     packed = _packed_stage2(op.a, exact=False)
     if op.bf16 and not packed:
         raise RuntimeError(f"bf16 operands: only the bf16 MFMA score kernel exists (relation rank a <= {_PACKED_MAX_C})")
     with torch.cuda.device(op.dev):
         sp = _stream_ptr(op.dev)
-        u = torch.empty((B, op.a), dtype=torch.float32, device=op.dev)
         qp = _packed_buffer(op.dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.a)) if packed else None
         ws = _pair_stage1(op, h, t, B, sp, u, qp)
         _stage2(op.bf16, sp, u, qp, op.R, out, flags)
         _strict_check(ws, sp)
+    return out, u
+
+
+def _f32_matrix(name, t, dev=None):
+    _require_gpu(name, t)
+    if t.dtype != torch.float32 or t.dim() != 2 or (dev is not None and t.device != dev):
+        raise RuntimeError(f"{name} must be a float32 matrix on {dev or 'the GPU'}, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
+
+
+def _ld(t):
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _pair_rows(core, X, x_idx, w, sp):
+    """``rtk_pair_rows_f32`` on the stream ``sp`` -> ``(rows (B, b) fp32, workspace)``."""
+    a, b, c = core.shape
+    B = w.shape[0]
+    rows = torch.empty((B, b), dtype=torch.float32, device=core.device)
+    ws = _workspace(core.device, sp, max(256, _size("rtk_pair_rows_workspace_bytes", B, a, b, c)))
+    _lib.check(_lib.load().rtk_pair_rows_f32(core.data_ptr(), a, b, c, X.data_ptr(), X.shape[0], x_idx.data_ptr(),
+                                             w.data_ptr(), _ld(w), B, rows.data_ptr(), b, ws.data_ptr(), ws.numel(), sp),
+               "rtk_pair_rows_f32")
+    return rows, ws
+
+
+@torch.no_grad()
+def pair_rows(core, X, x_idx, w):
+    """``rows[d, j] = sum_i w[d, i] * sum_k core[i, j, k] X[x_idx[d], k]`` -> ``(B, b)`` fp32 (``rtk_pair_rows_f32``): the
+    row gradients of relation prediction.  ``core`` (a, b, c), ``X`` (n, c) and ``w`` (B, a) are float32; ``c <= 208``,
+    ``c % 4 == 0``.  Nothing of size B x a*b is written; the bits of a row depend only on ``X[x_idx[d]]``, ``w[d]`` and
+    the core.  An id outside [0, n) is clamped and raises ``IndexError`` by the ``index_check`` policy."""
+    _require_gpu("core", core)
+    if core.dtype != torch.float32 or core.dim() != 3:
+        raise RuntimeError(f"core must be a float32 (a, b, c) tensor, got {core.dtype} {tuple(core.shape)}")
+    core, dev = core.contiguous(), core.device
+    X, w = _f32_matrix("X", X, dev).contiguous(), _f32_matrix("w", w, dev)
+    idx = _idx("x_idx", x_idx, dev)
+    if X.shape[1] != core.shape[2] or w.shape[1] != core.shape[0] or idx.numel() != w.shape[0]:
+        raise RuntimeError(f"X {tuple(X.shape)}, w {tuple(w.shape)} and x_idx ({idx.numel()},) do not match core "
+                           f"{tuple(core.shape)}")
+    with torch.cuda.device(dev):
+        sp = _stream_ptr(dev)
+        rows, ws = _pair_rows(core, X, idx, w, sp)
+        if w.shape[0] > 0:
+            _strict_check(ws, sp)
+    return rows
+
+
+@torch.no_grad()
+def core_outer(x, y, z):
+    """``gG[i, j, k] = sum_d (x[d, i] * y[d, j]) * z[d, k]`` -> ``(a, b, c)`` fp32 (``rtk_core_outer_f32``): the exact fp32
+    MFMA GEMM on the Khatri-Rao product of ``x`` (B, a) and ``y`` (B, b), which is never written to memory, against ``z``
+    (B, c).  One chain over d ascending per element: the bits of ``rtk_gemm_f32`` on the materialised product."""
+    x = _f32_matrix("x", x)
+    y, z = _f32_matrix("y", y, x.device), _f32_matrix("z", z, x.device)
+    if not x.shape[0] == y.shape[0] == z.shape[0]:
+        raise RuntimeError(f"x {tuple(x.shape)}, y {tuple(y.shape)}, z {tuple(z.shape)} must have one row per query")
+    a, b, c = x.shape[1], y.shape[1], z.shape[1]
+    gG = torch.empty((a, b, c), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().rtk_core_outer_f32(x.data_ptr(), _ld(x), a, y.data_ptr(), _ld(y), b, z.data_ptr(), _ld(z), c,
+                                                  x.shape[0], gG.data_ptr(), _stream_ptr(x.device)), "rtk_core_outer_f32")
+    return gG
+
+
+@torch.no_grad()
+def scatter_rows(idx, rows, n_out):
+    """``out[e, :] = sum_{d: idx[d] = e} rows[d, :]`` -> ``(n_out, n)`` fp32 (``rtk_scatter_rows_f32``): the ordered
+    scatter, no float atomics, the same bits on every run; ids outside [0, n_out) add nothing.  ``n <= 1024``."""
+    rows = _f32_matrix("rows", rows)
+    dev = rows.device
+    idx = _idx("idx", idx, dev)
+    B, n = rows.shape
+    if idx.numel() != B:
+        raise RuntimeError(f"idx has {idx.numel()} entries for {B} rows")
+    out = torch.empty((n_out, n), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(256, _size("rtk_scatter_rows_workspace_bytes", B)), dtype=torch.uint8, device=dev)
+        _lib.check(_lib.load().rtk_scatter_rows_f32(idx.data_ptr(), rows.data_ptr(), _ld(rows), B, n, n_out, out.data_ptr(),
+                                                    ws.data_ptr(), ws.numel(), _stream_ptr(dev)), "rtk_scatter_rows_f32")
     return out
+
+
+class _RelationLogits(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, core, R, S, O, subject_idx, object_idx):
+        op = _Operands(core, R, S, O)
+        h, t, B = _pair_queries(op, subject_idx, object_idx)
+        out, u = _relation_forward(op, h, t, B, _score_flags(False, None, torch.float32, op.bf16))
+        ctx.save_for_backward(op.core, op.R, op.S, op.O, h, t, u)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        core, R, S, O, h, t, u = ctx.saved_tensors
+        needs = ctx.needs_input_grad[:4]
+        pdt = core.dtype                      # bf16 operands: gradients computed in fp32, returned in bf16
+        B, dev = u.shape[0], u.device
+        if B == 0:
+            return tuple(torch.zeros_like(x) if n else None for x, n in zip((core, R, S, O), needs)) + (None, None)
+        if pdt == torch.bfloat16:
+            core, R, S, O = core.float(), R.float(), S.float(), O.float()
+        lib = _lib.load()
+        a, n_rel = core.shape[0], R.shape[0]
+        dZ = grad_out.contiguous().float()
+        g = [None] * 4
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            if needs[1]:                      # gR[r, i] = sum_d dZ[d, r] u[d, i]
+                g[1] = torch.empty((n_rel, a), dtype=torch.float32, device=dev)
+                _lib.check(lib.rtk_gemm_f32(dZ.data_ptr(), 0, n_rel, u.data_ptr(), 0, a, g[1].data_ptr(), a, n_rel, a, B, 0,
+                                            sp), "rtk_gemm_f32 (gR)")
+            if needs[0] or needs[2] or needs[3]:
+                du = torch.empty((B, a), dtype=torch.float32, device=dev)      # du[d, i] = sum_r dZ[d, r] R[r, i]
+                _lib.check(lib.rtk_gemm_f32(dZ.data_ptr(), 1, n_rel, R.data_ptr(), 0, a, du.data_ptr(), a, B, a, n_rel, 0,
+                                            sp), "rtk_gemm_f32 (du)")
+            if needs[2]:
+                g[2] = scatter_rows(h, _pair_rows(core, O, t, du, sp)[0], S.shape[0])
+            if needs[3]:
+                g[3] = scatter_rows(t, _pair_rows(core.transpose(1, 2).contiguous(), S, h, du, sp)[0], O.shape[0])
+            if needs[0]:                      # (ids outside their table were reported by the forward; here they are clamped)
+                g[0] = core_outer(du, S.index_select(0, h.clamp(0, S.shape[0] - 1)),
+                                  O.index_select(0, t.clamp(0, O.shape[0] - 1)))
+        if pdt == torch.bfloat16:
+            g = [x.to(pdt) if x is not None else None for x in g]
+        # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
+        return tuple(g) + (None, None)
+
+
+def relation_logits(core, R, S, O, subject_idx, object_idx):
+    """Logits of every relation for a batch of (h, ?, t) queries -> ``(B, n_rel)`` fp32, with gradients in core, R, S and
+    O: the forward is ``score_relations(..., sigmoid=False)`` (the same bits).  The backward writes nothing of size
+    B x a*b: ``du = dZ . R`` and ``gR = dZ^T . u`` by ``rtk_gemm_f32``, the row gradients of ``S[h]`` and ``O[t]`` by
+    ``rtk_pair_rows_f32`` and the ordered ``rtk_scatter_rows_f32``, the core's by ``rtk_core_outer_f32``; only what
+    ``requires_grad`` asks for is computed, and two runs give the same bits.  bf16 operands: the forward runs the bf16
+    kernels, the backward in fp32 on the upcast operands, gradients returned in bf16.  Symmetric model: pass ``S is O``;
+    autograd adds the two gradients.  Limit: the fp32 sweeps of the backward need ``b = c <= 208`` and ``c % 4 == 0``
+    (anything else raises; no fallback)."""
+    return _RelationLogits.apply(core, R, S, O, subject_idx, object_idx)
+
+
+def relation_ce_loss(core, R, S, O, subject_idx, object_idx, relation_idx, label_smoothing=0.0):
+    """Relation-classification loss: the mean softmax cross-entropy of ``relation_logits`` against ``relation_idx``
+    (``F.cross_entropy`` on the small (B, n_rel) matrix).  Stands alone or as the auxiliary term next to ``bce_loss_1vN``."""
+    z = relation_logits(core, R, S, O, subject_idx, object_idx)
+    rel = _idx("relation_idx", relation_idx, z.device)
+    if rel.numel() != z.shape[0]:
+        raise RuntimeError(f"relation_idx has {rel.numel()} entries for {z.shape[0]} queries")
+    return torch.nn.functional.cross_entropy(z, rel, label_smoothing=label_smoothing)
 
 
 def cg_fifth_group_columns(N, c, flags=0):
