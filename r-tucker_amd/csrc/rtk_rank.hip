@@ -107,12 +107,26 @@ __global__ __launch_bounds__(256) void target_scores_kernel(const float *__restr
     pt_out[d] = (j >= 0 && j < N) ? P[(int64_t)d * ld + j] : -INFINITY;
 }
 
+// acc[k] += the workgroup's sum of v[k], k < K: over each wave by shuffle, then over the 4 waves in wave order.  One
+// workgroup and stream-ordered launches: no atomics needed.
+template <int K>
+__device__ __forceinline__ void block_sum_into(double *__restrict__ acc, double (&v)[K]) {
+    __shared__ double s[4][K];
+    const int t = threadIdx.x;
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
+        if ((t & 63) == 0) s[t >> 6][k] = v[k];
+    }
+    __syncthreads();
+    if (t < K) acc[t] += s[0][t] + s[1][t] + s[2][t] + s[3][t];
+}
+
 // acc[0] += sum 1/rank, acc[1..3] += #(rank <= 1 / 3 / 10), acc[4] += sum of the BCE row sums
 // (src/utils/metrics.py:4-22 returns exactly these batch sums; train.py:118-121 adds them up)
-__global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t *__restrict__ ranks,
-                                                           const double *__restrict__ bce_rows, int B,
-                                                           double *__restrict__ acc, double bce_scale) {
-    __shared__ double s[4][5];
+__global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t *__restrict__ ranks, const double *__restrict__ bce_rows,
+                                                           int B, double *__restrict__ acc, double bce_scale) {
     const int t = threadIdx.x;
     double v[5] = {0, 0, 0, 0, 0};
     for (int d = t; d < B; d += 256) {
@@ -123,27 +137,15 @@ __global__ __launch_bounds__(256) void rank_metrics_kernel(const int32_t *__rest
         v[3] += rk <= 10;
         if (bce_rows) v[4] += bce_rows[d] * bce_scale;
     }
-#pragma unroll
-    for (int k = 0; k < 5; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-        if ((t & 63) == 0) s[t >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (t < 5) acc[t] += s[0][t] + s[1][t] + s[2][t] + s[3][t];   // one workgroup, launches are stream-ordered: no atomics needed
+    block_sum_into(acc, v);
 }
 
 // acc[4 k + 0 .. 3] += sum 1/rank, #(rank <= 1 / 3 / 10) of the optimistic (k = 0: 1 + greater), realistic
 // (k = 1: 1 + greater + equal / 2) and pessimistic (k = 2: 1 + greater + equal) ranks; acc[12] += #(equal > 0).
-// rank_metrics_kernel's reduction: one workgroup, a fixed order.
-__global__ __launch_bounds__(256) void tie_metrics_kernel(const int32_t *__restrict__ greater,
-                                                          const int32_t *__restrict__ equal, int B,
-                                                          double *__restrict__ acc) {
-    __shared__ double s[4][13];
+__global__ __launch_bounds__(256) void tie_metrics_kernel(const int32_t *__restrict__ greater, const int32_t *__restrict__ equal,
+                                                          int B, double *__restrict__ acc) {
     const int t = threadIdx.x;
-    double v[13];
-#pragma unroll
-    for (int k = 0; k < 13; ++k) v[k] = 0.0;
+    double v[13] = {};
     for (int d = t; d < B; d += 256) {
         const double g = (double)greater[d], e = (double)equal[d];
 #pragma unroll
@@ -156,14 +158,17 @@ __global__ __launch_bounds__(256) void tie_metrics_kernel(const int32_t *__restr
         }
         v[12] += e > 0.0;
     }
-#pragma unroll
-    for (int k = 0; k < 13; ++k) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_xor(v[k], o);
-        if ((t & 63) == 0) s[t >> 6][k] = v[k];
-    }
-    __syncthreads();
-    if (t < 13) acc[t] += s[0][t] + s[1][t] + s[2][t] + s[3][t];
+    block_sum_into(acc, v);
+}
+
+// the refusals of the entries that rank on a stored (batch, n) score block; `operands`: the entry's pointers are there
+int check_stored(const char *fn, bool operands, int64_t batch, int64_t n, int64_t ld, int64_t col0, const int64_t *pair_slot,
+                 const int64_t *pair_ptr, const int64_t *pair_obj) {
+    RTK_REQUIRE(operands, RTK_ERR_BAD_ARG, "%s: null operand", fn);
+    RTK_REQUIRE(batch > 0 && n > 0 && ld >= n && col0 >= 0, RTK_ERR_BAD_ARG, "%s: bad sizes", fn);
+    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "%s: pair_slot without the CSR arrays", fn);
+    RTK_REQUIRE(batch < (1ll << 31) && n < (1ll << 31), RTK_ERR_UNSUPPORTED, "%s: dimension too large", fn);
+    return RTK_OK;
 }
 
 }  // namespace
@@ -203,10 +208,8 @@ extern "C" int rtk_filtered_rank_partial_f32(const float *P, int64_t batch, int6
                                              const float *target_scores, const int64_t *obj_idx,
                                              const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
                                              int32_t *counts_out, double *bce_rows_out, void *stream) {
-    RTK_REQUIRE(P && obj_idx && counts_out && target_scores, RTK_ERR_BAD_ARG, "rtk_filtered_rank_partial_f32: null operand");
-    RTK_REQUIRE(batch > 0 && n_local > 0 && ld >= n_local && col0 >= 0, RTK_ERR_BAD_ARG, "rtk_filtered_rank_partial_f32: bad sizes");
-    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "rtk_filtered_rank_partial_f32: pair_slot without the CSR arrays");
-    RTK_REQUIRE(batch < (1ll << 31) && n_local < (1ll << 31), RTK_ERR_UNSUPPORTED, "rtk_filtered_rank_partial_f32: dimension too large");
+    if (const int rc = check_stored("rtk_filtered_rank_partial_f32", P && obj_idx && counts_out && target_scores, batch,
+                                    n_local, ld, col0, pair_slot, pair_ptr, pair_obj)) return rc;
     hipLaunchKernelGGL(filtered_rank_kernel<true>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, P, (int)batch,
                        (int)n_local, ld, col0, target_scores, obj_idx, pair_slot, pair_ptr, pair_obj, counts_out, bce_rows_out,
                        (int32_t *)nullptr);
@@ -218,10 +221,8 @@ extern "C" int rtk_filtered_tie_counts_partial_f32(const float *P, int64_t batch
                                                    const int64_t *pair_slot, const int64_t *pair_ptr,
                                                    const int64_t *pair_obj, int32_t *greater_out, int32_t *equal_out,
                                                    void *stream) {
-    RTK_REQUIRE(P && obj_idx && greater_out && equal_out && target_scores, RTK_ERR_BAD_ARG, "rtk_filtered_tie_counts_partial_f32: null operand");
-    RTK_REQUIRE(batch > 0 && n_local > 0 && ld >= n_local && col0 >= 0, RTK_ERR_BAD_ARG, "rtk_filtered_tie_counts_partial_f32: bad sizes");
-    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "rtk_filtered_tie_counts_partial_f32: pair_slot without the CSR arrays");
-    RTK_REQUIRE(batch < (1ll << 31) && n_local < (1ll << 31), RTK_ERR_UNSUPPORTED, "rtk_filtered_tie_counts_partial_f32: dimension too large");
+    if (const int rc = check_stored("rtk_filtered_tie_counts_partial_f32", P && obj_idx && greater_out && equal_out && target_scores,
+                                    batch, n_local, ld, col0, pair_slot, pair_ptr, pair_obj)) return rc;
     hipLaunchKernelGGL((filtered_rank_kernel<true, true>), dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, P,
                        (int)batch, (int)n_local, ld, col0, target_scores, obj_idx, pair_slot, pair_ptr, pair_obj, greater_out,
                        (double *)nullptr, equal_out);
@@ -232,10 +233,8 @@ extern "C" int rtk_filtered_rank_f32(const float *P, int64_t batch, int64_t n_en
                                      const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
                                      const int64_t *pair_obj, int32_t *ranks_out, double *bce_rows_out,
                                      void *stream) {
-    RTK_REQUIRE(P && obj_idx && ranks_out, RTK_ERR_BAD_ARG, "rtk_filtered_rank_f32: null operand");
-    RTK_REQUIRE(batch > 0 && n_ent > 0 && ld >= n_ent, RTK_ERR_BAD_ARG, "rtk_filtered_rank_f32: bad sizes");
-    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "rtk_filtered_rank_f32: pair_slot without the CSR arrays");
-    RTK_REQUIRE(batch < (1ll << 31) && n_ent < (1ll << 31), RTK_ERR_UNSUPPORTED, "rtk_filtered_rank_f32: dimension too large");
+    if (const int rc = check_stored("rtk_filtered_rank_f32", P && obj_idx && ranks_out, batch, n_ent, ld, 0, pair_slot, pair_ptr,
+                                    pair_obj)) return rc;
     hipLaunchKernelGGL(filtered_rank_kernel<false>, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, P, (int)batch,
                        (int)n_ent, ld, (int64_t)0, (const float *)nullptr, obj_idx, pair_slot, pair_ptr, pair_obj, ranks_out,
                        bce_rows_out, (int32_t *)nullptr);

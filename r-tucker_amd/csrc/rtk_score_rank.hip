@@ -13,11 +13,14 @@
 // rtk_score_rank_* is the one-block call: both steps at col0 = 0, n_local = n_ent, pt kept in the workspace and the
 // finish pass writing 1 + count.  There is one set of kernels.
 //
-// rtk_score_rank_tie_counts_* is step 2 with the two counts of the tie-aware ranks in place of their stable combination:
+// Step 2 has three modes (Stable, StableBce, Ties below), chosen at compile time by the entry point.  The stable modes
+// give the count above, StableBce with the rows' BCE sums; rtk_score_rank_tie_counts_* is the Ties mode: the two counts
+// of the tie-aware ranks in place of their stable combination,
 //
 //   greater = #{ j != t : p'_j > pt }      equal = #{ j != t : p'_j == pt }      (1 + greater <= rank <= 1 + greater + equal)
 //
-// from the TIES instantiations of count_kernel and filter_kernel and from finish_ties_kernel.
+// Every mode keeps two planes of partials: int32 counts, and a second plane whose element type the mode names -- float
+// BCE sums or int32 `equal` counts.
 //
 // Step 1 is target_kernel: one wave per query, p_t from a 32x32 MFMA tile whose rows are all query d and whose column 0
 // is O[t_d].  Step 2 is three launches on the caller's stream:
@@ -33,7 +36,8 @@
 //                   query tiles are cut into ranges so that the chip stays full.
 //   filter_kernel   RP_UQ waves per query: wave u re-scores the query's CSR entries [32 (u + RP_UQ k), +32) that fall in
 //                   the block and takes them out of (or keeps them in) the count as filtered_rank_kernel does.
-//   finish_kernel   partials of the slots and of the filter waves added in a fixed order; base + count written.
+//   finish_kernel   partials of the slots and of the filter waves added in a fixed order; base + count written, and
+//                   the second plane's sum (-BCE row sum, or `equal`) by the modes that have one.
 //
 // Exactness.  Every probability comes from Frag<T, KS> (rtk_score_rank_kernel.h).  A score's bits depend only on its
 // query row, its entity row and c: an MFMA output element does not depend on its position in the tile, the O row
@@ -54,6 +58,29 @@ namespace {
 constexpr int RP_WAVES = SW_WAVES;             // the counting kernel is a sweep: 128 entity rows per tile
 constexpr int RP_SLOTS = SW_SLOTS;             // rows of partials: the resident workgroups, two per CU
 constexpr int RP_UQ = 8;                       // filter waves per query
+
+// The modes of step 2.  second_t: what the second plane of partials holds (of the slots and of the filter waves);
+// sum_t: what the finish pass adds them up in and writes out.
+struct Stable {                                // base + #{p' > pt} + #{j < t : p' == pt}
+    typedef float second_t;                    // (unused)
+    typedef double sum_t;
+    static constexpr bool BCE = false, TIES = false;
+};
+struct StableBce {                             // the same, and the rows' BCE sums
+    typedef float second_t;                    // float BCE partials
+    typedef double sum_t;
+    static constexpr bool BCE = true, TIES = false;
+};
+struct Ties {                                  // greater = #{j != t : p' > pt} and equal = #{j != t : p' == pt}
+    typedef int32_t second_t;                  // `equal` counts
+    typedef int32_t sum_t;
+    static constexpr bool BCE = false, TIES = true;
+};
+// the stable mode a call's bce_rows selects
+template <typename F>
+int stable_mode(const double *bce_rows, F f) {
+    return bce_rows ? f(StableBce{}) : f(Stable{});
+}
 
 // the queried object's id as every kernel here sees it: clamped into [0, n_ent) (an id outside sets bit 2 of the error
 // word in target_kernel)
@@ -98,21 +125,21 @@ struct CountLds {
 // counted, never stored.  A lane holds one entity and 16 query rows: the 16 counts (and BCE terms) are summed over the
 // 32 entity lanes by the butterfly, over the 4 waves in wave order, and added to the workgroup's own row of partials.
 //
-// TIES: the two counts of the tie-aware ranks instead (rtk_score_rank_tie_counts_*): an element contributes p > pt and
+// Ties: the two counts of the tie-aware ranks instead (rtk_score_rank_tie_counts_*): an element contributes p > pt and
 // (p == pt) & (j != t).  A 32-lane sum of either is at most 32 and the sum over the 4 waves at most 128, so both travel
 // as one int (greater | equal << 16) through the butterfly and the LDS slot -- the exchanges and the LDS of the plain
-// count -- and publish unpacks them into two int32 planes (totals reach n_local): greater into part_cnt, equal into
-// the plane that holds the BCE partials otherwise (the same size).
-template <typename T, int KS, int SG, bool BCE, bool TIES = false>
+// count -- and publish unpacks them into the mode's two int32 planes (totals reach n_local): greater into part_cnt,
+// equal into part_second.
+template <typename T, int KS, int SG, typename Mode>
 struct CountSweep {
-    static_assert(!(BCE && TIES), "the tie counts come without BCE sums");
+    static constexpr bool BCE = Mode::BCE, TIES = Mode::TIES;
     typedef CountLds<T, KS> L;
     static constexpr int EXTRA = L::EXTRA;
     int B, col0, n_ent;
     const int64_t *__restrict__ obj_idx;
     const float *__restrict__ pt_in;
     int32_t *__restrict__ part_cnt;
-    float *__restrict__ part_bce;
+    typename Mode::second_t *__restrict__ part_second;
     float stg_pt = 0.f;
 
     __device__ __forceinline__ void load_extra(SweepLane ln, int mt) {
@@ -167,11 +194,11 @@ struct CountSweep {
             const int d = mt * 32 + r;
             if (d < B) {
                 const int64_t at = (int64_t)slot * B + d;
-                if (TIES) {                                        // half 0: greater, half 1: equal
+                if constexpr (TIES) {                              // half 0: greater, half 1: equal
                     const int *rc = reinterpret_cast<const int *>(sweep_lds + L::RED + cur * L::RED_BUF);
                     const int both = rc[r] + rc[32 + r] + rc[64 + r] + rc[96 + r];
                     const int s = h == 0 ? (both & 0xffff) : (both >> 16);
-                    int32_t *plane = h == 0 ? part_cnt : reinterpret_cast<int32_t *>(part_bce);
+                    int32_t *plane = h == 0 ? part_cnt : part_second;
                     plane[at] = first ? s : plane[at] + s;
                 } else if (h == 0) {
                     const int *rc = reinterpret_cast<const int *>(sweep_lds + L::RED + cur * L::RED_BUF);
@@ -180,7 +207,7 @@ struct CountSweep {
                 } else {
                     const float *rb = reinterpret_cast<const float *>(sweep_lds + L::RED + (2 + cur) * L::RED_BUF);
                     const float s = ((rb[r] + rb[32 + r]) + rb[64 + r]) + rb[96 + r];
-                    part_bce[at] = first ? s : part_bce[at] + s;
+                    part_second[at] = first ? s : part_second[at] + s;
                 }
             }
         }
@@ -188,22 +215,24 @@ struct CountSweep {
 };
 
 // Step 2, dense part.  Workgroup (slot, qs): entity tiles slot, slot + n_slots, ...; query tiles of range qs.
-template <typename T, int KS, int SG, bool BCE, bool TIES = false>
+template <typename T, int KS, int SG, typename Mode>
 __global__ __launch_bounds__(64 * RP_WAVES, 2) void count_kernel(const unsigned char *__restrict__ qp, int B,
                                                                  const T *__restrict__ O, int n_local, int c, int col0,
                                                                  int n_ent, const int64_t *__restrict__ obj_idx,
                                                                  const float *__restrict__ pt_in, int n_slots, int qsplit,
                                                                  int32_t *__restrict__ part_cnt,
-                                                                 float *__restrict__ part_bce, bool vec) {
-    CountSweep<T, KS, SG, BCE, TIES> pol{B, col0, n_ent, obj_idx, pt_in, part_cnt, part_bce};
+                                                                 typename Mode::second_t *__restrict__ part_second,
+                                                                 bool vec) {
+    CountSweep<T, KS, SG, Mode> pol{B, col0, n_ent, obj_idx, pt_in, part_cnt, part_second};
     sweep<T, KS, SG>(pol, qp, B, O, n_local, c, vec, n_slots, qsplit);
 }
 
 // Step 2, the filter correction: wave u of query d scores the CSR entries [i0 + 32 (u + RP_UQ k), + 32) of the query,
 // one per column, and corrects the count for those inside the block (filtered_rank_kernel's rule, global ids).
-// TIES: the corrections of the two tie counts -- the entry leaves `greater` or `equal` and, now a 0, joins `equal` when
-// the target score is 0 -- as ints in fc_cnt (greater) and fc_bce (equal).
-template <typename T, int KS, int SG, bool TIES = false>
+// The correction depends on the mode only through what the second plane holds.  float (the stable modes): the entries'
+// BCE terms when want_bce.  int32 (Ties): the corrections of the two tie counts -- the entry leaves `greater` or `equal`
+// and, now a 0, joins `equal` when the target score is 0 -- in fc_cnt (greater) and fc_second (equal).
+template <typename T, int KS, int SG, typename Second>
 __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned char *__restrict__ qp, int B,
                                                                const T *__restrict__ O, int n_local, int c, int col0,
                                                                int n_ent, const int64_t *__restrict__ obj_idx,
@@ -211,8 +240,9 @@ __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned ch
                                                                const int64_t *__restrict__ pair_slot,
                                                                const int64_t *__restrict__ pair_ptr,
                                                                const int64_t *__restrict__ pair_obj,
-                                                               int32_t *__restrict__ fc_cnt, float *__restrict__ fc_bce,
-                                                               bool want_bce, bool vec) {
+                                                               int32_t *__restrict__ fc_cnt,
+                                                               Second *__restrict__ fc_second, bool want_bce, bool vec) {
+    constexpr bool TIES = std::is_same<Second, int32_t>::value;
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane((int)blockIdx.x * RP_WAVES + (int)(threadIdx.x >> 6));
     const int d = w / RP_UQ, u = w % RP_UQ;
@@ -259,95 +289,61 @@ __global__ __launch_bounds__(64 * RP_WAVES) void filter_kernel(const unsigned ch
     }
     if (lane == 0) {
         fc_cnt[(int64_t)d * RP_UQ + u] = cnt;
-        fc_bce[(int64_t)d * RP_UQ + u] = TIES ? __int_as_float(eq) : bce;
+        if constexpr (TIES) fc_second[(int64_t)d * RP_UQ + u] = eq;
+        else fc_second[(int64_t)d * RP_UQ + u] = bce;
     }
 }
 
 // counts_out[d] = base + partials of the slots + the filter waves' corrections (base 0: a block's count; base 1: the
-// whole range's rank); bce_rows_out[d] = -(the same of the BCE sums).
+// whole range's rank); second_out[d] = the same of the second plane, by the modes that have one: StableBce -(the BCE
+// sums), floats added as doubles; Ties the `equal` counts.
 // 32 queries per workgroup, 8 threads per query take the slots 8 apart; everything is added in a fixed order.
+template <typename Mode>
 __global__ __launch_bounds__(256) void finish_kernel(int B, int n_slots, int col0, int n_local, int n_ent, int base,
                                                      const int32_t *__restrict__ part_cnt,
-                                                     const float *__restrict__ part_bce,
-                                                     const int32_t *__restrict__ fc_cnt, const float *__restrict__ fc_bce,
+                                                     const typename Mode::second_t *__restrict__ part_second,
+                                                     const int32_t *__restrict__ fc_cnt,
+                                                     const typename Mode::second_t *__restrict__ fc_second,
                                                      const int64_t *__restrict__ obj_idx,
                                                      const int64_t *__restrict__ pair_slot,
                                                      const float *__restrict__ pt_in, int32_t *__restrict__ counts_out,
-                                                     double *__restrict__ bce_rows_out) {
+                                                     typename Mode::sum_t *__restrict__ second_out) {
+    typedef typename Mode::sum_t sum_t;
+    constexpr bool SECOND = Mode::BCE || Mode::TIES;
     __shared__ int s_cnt[8][32];
-    __shared__ double s_bce[8][32];
+    __shared__ sum_t s_sec[8][32];
     const int t = threadIdx.x, q = t & 31, sl = t >> 5;
     const int d = min((int)blockIdx.x * 32 + q, B - 1);
-    const bool want_bce = bce_rows_out != nullptr;
     int cnt = 0;
-    double bce = 0.0;
+    sum_t sec = 0;
     for (int k = sl; k < n_slots; k += 8) {
         cnt += part_cnt[(int64_t)k * B + d];
-        if (want_bce) bce += (double)part_bce[(int64_t)k * B + d];
+        if (SECOND) sec += (sum_t)part_second[(int64_t)k * B + d];
     }
     s_cnt[sl][q] = cnt;
-    s_bce[sl][q] = bce;
+    if (SECOND) s_sec[sl][q] = sec;
     __syncthreads();
     if (sl != 0 || (int)blockIdx.x * 32 + q >= B) return;
     cnt = 0;
-    bce = 0.0;
+    sec = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         cnt += s_cnt[k][q];
-        bce += s_bce[k][q];
-    }
-    const bool listed = pair_slot && pair_slot[d] >= 0;
-    if (listed) {
-#pragma unroll
-        for (int u = 0; u < RP_UQ; ++u) {
-            cnt += fc_cnt[(int64_t)d * RP_UQ + u];
-            if (want_bce) bce += (double)fc_bce[(int64_t)d * RP_UQ + u];
-        }
-    } else if (want_bce) {                                   // no filter list: the queried object is the only positive
-        const int jl = clamp_target(obj_idx[d], n_ent) - col0;
-        const float pt = pt_in[d];
-        if (jl >= 0 && jl < n_local) bce += (double)(rtk_clog(pt) - rtk_clog(1.0f - pt));
-    }
-    counts_out[d] = base + cnt;
-    if (want_bce) bce_rows_out[d] = -bce;
-}
-
-// The finish pass of the tie counts: greater_out[d] / equal_out[d] = partials of the slots + the filter waves'
-// corrections, in finish_kernel's layout and order (32 queries per workgroup, 8 threads per query).
-__global__ __launch_bounds__(256) void finish_ties_kernel(int B, int n_slots, const int32_t *__restrict__ part_gt,
-                                                          const int32_t *__restrict__ part_eq,
-                                                          const int32_t *__restrict__ fc_gt,
-                                                          const int32_t *__restrict__ fc_eq,
-                                                          const int64_t *__restrict__ pair_slot,
-                                                          int32_t *__restrict__ greater_out,
-                                                          int32_t *__restrict__ equal_out) {
-    __shared__ int s_gt[8][32], s_eq[8][32];
-    const int t = threadIdx.x, q = t & 31, sl = t >> 5;
-    const int d = min((int)blockIdx.x * 32 + q, B - 1);
-    int gt = 0, eq = 0;
-    for (int k = sl; k < n_slots; k += 8) {
-        gt += part_gt[(int64_t)k * B + d];
-        eq += part_eq[(int64_t)k * B + d];
-    }
-    s_gt[sl][q] = gt;
-    s_eq[sl][q] = eq;
-    __syncthreads();
-    if (sl != 0 || (int)blockIdx.x * 32 + q >= B) return;
-    gt = eq = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-        gt += s_gt[k][q];
-        eq += s_eq[k][q];
+        if (SECOND) sec += s_sec[k][q];
     }
     if (pair_slot && pair_slot[d] >= 0) {
 #pragma unroll
         for (int u = 0; u < RP_UQ; ++u) {
-            gt += fc_gt[(int64_t)d * RP_UQ + u];
-            eq += fc_eq[(int64_t)d * RP_UQ + u];
+            cnt += fc_cnt[(int64_t)d * RP_UQ + u];
+            if (SECOND) sec += (sum_t)fc_second[(int64_t)d * RP_UQ + u];
         }
+    } else if (Mode::BCE) {                                  // no filter list: the queried object is the only positive
+        const int jl = clamp_target(obj_idx[d], n_ent) - col0;
+        const float pt = pt_in[d];
+        if (jl >= 0 && jl < n_local) sec += (sum_t)(rtk_clog(pt) - rtk_clog(1.0f - pt));
     }
-    greater_out[d] = gt;
-    equal_out[d] = eq;
+    counts_out[d] = base + cnt;
+    if (SECOND) second_out[d] = Mode::BCE ? -sec : sec;
 }
 
 struct PartLayout {
@@ -373,58 +369,31 @@ int launch_targets(const unsigned char *qp, int B, const T *O, int n_local, int 
     return RTK_OK;
 }
 
-// Step 2 on the stream: count_kernel, filter_kernel when there is a filter, finish_kernel writing base + count.
-template <typename T, int KS, int SG>
+// Step 2 on the stream: count_kernel, filter_kernel when there is a filter, finish_kernel writing base + count and the
+// mode's second output.  The second planes get the mode's element type here, once.
+template <typename T, int KS, int SG, typename Mode>
 int launch_counts(const unsigned char *qp, int B, const T *O, int n_local, int c, int col0, int n_ent, const float *pt,
                   const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
-                  int base, int32_t *counts, double *bce_rows, unsigned char *ws, hipStream_t st, const char *fn) {
+                  int base, int32_t *counts, typename Mode::sum_t *second_out, unsigned char *ws, hipStream_t st,
+                  const char *fn) {
+    typedef typename Mode::second_t second_t;
     const PartLayout L = layout_of(B, n_local);
     const SweepGrid g = grid_of(B, n_local, RP_SLOTS);
     int32_t *pcnt = reinterpret_cast<int32_t *>(ws + L.cnt);
-    float *pbce = reinterpret_cast<float *>(ws + L.bce);
+    second_t *psec = reinterpret_cast<second_t *>(ws + L.bce);
     int32_t *fcnt = reinterpret_cast<int32_t *>(ws + L.fcnt);
-    float *fbce = reinterpret_cast<float *>(ws + L.fbce);
+    second_t *fsec = reinterpret_cast<second_t *>(ws + L.fbce);
     const bool vec = vec_rows(O, c);
-    const auto count = [&](auto BCE) {
-        return launch_lds<&count_kernel<T, KS, SG, BCE.value>, CountLds<T, KS>::TOTAL>(
-            dim3((unsigned)(g.n_slots * g.qsplit)), dim3(64 * RP_WAVES), st, fn, qp, B, O, n_local, c, col0, n_ent, obj_idx, pt,
-            g.n_slots, g.qsplit, pcnt, pbce, vec);
-    };
-    const int rc = bce_rows ? count(std::true_type{}) : count(std::false_type{});
-    if (rc != RTK_OK) return rc;
-    if (pair_slot)
-        hipLaunchKernelGGL((filter_kernel<T, KS, SG>), dim3((unsigned)rtk_cdiv((int64_t)B * RP_UQ, RP_WAVES)),
-                           dim3(64 * RP_WAVES), 0, st, qp, B, O, n_local, c, col0, n_ent, obj_idx, pt, pair_slot, pair_ptr,
-                           pair_obj, fcnt, fbce, bce_rows != nullptr, vec);
-    hipLaunchKernelGGL(finish_kernel, dim3((unsigned)rtk_cdiv(B, 32)), dim3(256), 0, st, B, g.n_slots, col0, n_local, n_ent,
-                       base, pcnt, pbce, fcnt, fbce, obj_idx, pair_slot, pt, counts, bce_rows);
-    return RTK_OK;
-}
-
-// The tie counts on the stream: count_kernel and filter_kernel in their TIES forms on the block layout (the BCE planes
-// hold the equal counts), finish_ties_kernel.
-template <typename T, int KS, int SG>
-int launch_ties(const unsigned char *qp, int B, const T *O, int n_local, int c, int col0, int n_ent, const float *pt,
-                const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
-                int32_t *greater, int32_t *equal, unsigned char *ws, hipStream_t st, const char *fn) {
-    const PartLayout L = layout_of(B, n_local);
-    const SweepGrid g = grid_of(B, n_local, RP_SLOTS);
-    int32_t *pgt = reinterpret_cast<int32_t *>(ws + L.cnt);
-    float *peq = reinterpret_cast<float *>(ws + L.bce);
-    int32_t *fgt = reinterpret_cast<int32_t *>(ws + L.fcnt);
-    float *feq = reinterpret_cast<float *>(ws + L.fbce);
-    const bool vec = vec_rows(O, c);
-    const int rc = launch_lds<&count_kernel<T, KS, SG, false, true>, CountLds<T, KS>::TOTAL>(
+    const int rc = launch_lds<&count_kernel<T, KS, SG, Mode>, CountLds<T, KS>::TOTAL>(
         dim3((unsigned)(g.n_slots * g.qsplit)), dim3(64 * RP_WAVES), st, fn, qp, B, O, n_local, c, col0, n_ent, obj_idx, pt,
-        g.n_slots, g.qsplit, pgt, peq, vec);
+        g.n_slots, g.qsplit, pcnt, psec, vec);
     if (rc != RTK_OK) return rc;
     if (pair_slot)
-        hipLaunchKernelGGL((filter_kernel<T, KS, SG, true>), dim3((unsigned)rtk_cdiv((int64_t)B * RP_UQ, RP_WAVES)),
+        hipLaunchKernelGGL((filter_kernel<T, KS, SG, second_t>), dim3((unsigned)rtk_cdiv((int64_t)B * RP_UQ, RP_WAVES)),
                            dim3(64 * RP_WAVES), 0, st, qp, B, O, n_local, c, col0, n_ent, obj_idx, pt, pair_slot, pair_ptr,
-                           pair_obj, fgt, feq, false, vec);
-    hipLaunchKernelGGL(finish_ties_kernel, dim3((unsigned)rtk_cdiv(B, 32)), dim3(256), 0, st, B, g.n_slots, pgt,
-                       reinterpret_cast<const int32_t *>(peq), fgt, reinterpret_cast<const int32_t *>(feq), pair_slot, greater,
-                       equal);
+                           pair_obj, fcnt, fsec, Mode::BCE, vec);
+    hipLaunchKernelGGL(finish_kernel<Mode>, dim3((unsigned)rtk_cdiv(B, 32)), dim3(256), 0, st, B, g.n_slots, col0, n_local,
+                       n_ent, base, pcnt, psec, fcnt, fsec, obj_idx, pair_slot, pt, counts, second_out);
     return RTK_OK;
 }
 
@@ -450,36 +419,23 @@ int rank_targets(const char *fn, const void *q_packed, int64_t batch, int c, con
     });
 }
 
-template <typename T>
+// Step 2 of a block in one mode.  Stable: second_out is unused; StableBce: the BCE row sums; Ties: counts_out is
+// `greater`, second_out `equal`, and both are required.
+template <typename T, typename Mode>
 int rank_counts(const char *fn, const void *q_packed, int64_t batch, int c, const T *O, int64_t n_local, int64_t col0,
                 int64_t n_ent, const float *pt, const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
-                const int64_t *pair_obj, unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
-                size_t ws_bytes, void *stream) {
-    RTK_REQUIRE(pt, RTK_ERR_BAD_ARG, "%s: null operand", fn);
-    RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "%s: pair_slot without the CSR arrays", fn);
-    const int rc = check_rank<T>(fn, q_packed, batch, c, O, n_local, col0, n_ent, obj_idx, flags, counts_out, workspace, ws_bytes);
-    if (rc != RTK_OK || batch == 0) return rc;
-    return dispatch<T>(fn, c, flags, [&](auto K, auto SG) {
-        return launch_counts<T, K.value, SG.value>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c, (int)col0,
-                                                   (int)n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, 0, counts_out,
-                                                   bce_rows_out, (unsigned char *)workspace, (hipStream_t)stream, fn);
-    });
-}
-
-template <typename T>
-int rank_tie_counts(const char *fn, const void *q_packed, int64_t batch, int c, const T *O, int64_t n_local, int64_t col0,
-                    int64_t n_ent, const float *pt, const int64_t *obj_idx, const int64_t *pair_slot,
-                    const int64_t *pair_ptr, const int64_t *pair_obj, unsigned flags, int32_t *greater_out,
-                    int32_t *equal_out, void *workspace, size_t ws_bytes, void *stream) {
+                const int64_t *pair_obj, unsigned flags, int32_t *counts_out, typename Mode::sum_t *second_out,
+                void *workspace, size_t ws_bytes, void *stream) {
     RTK_REQUIRE(pt, RTK_ERR_BAD_ARG, "%s: null operand", fn);
     RTK_REQUIRE(!pair_slot || (pair_ptr && pair_obj), RTK_ERR_BAD_ARG, "%s: pair_slot without the CSR arrays", fn);
     const int rc = check_rank<T>(fn, q_packed, batch, c, O, n_local, col0, n_ent, obj_idx, flags,
-                                  equal_out ? greater_out : nullptr, workspace, ws_bytes);
+                                  Mode::TIES && !second_out ? nullptr : counts_out, workspace, ws_bytes);
     if (rc != RTK_OK || batch == 0) return rc;
     return dispatch<T>(fn, c, flags, [&](auto K, auto SG) {
-        return launch_ties<T, K.value, SG.value>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c, (int)col0,
-                                                 (int)n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, greater_out,
-                                                 equal_out, (unsigned char *)workspace, (hipStream_t)stream, fn);
+        return launch_counts<T, K.value, SG.value, Mode>((const unsigned char *)q_packed, (int)batch, O, (int)n_local, c,
+                                                         (int)col0, (int)n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj,
+                                                         0, counts_out, second_out, (unsigned char *)workspace,
+                                                         (hipStream_t)stream, fn);
     });
 }
 
@@ -499,8 +455,10 @@ int score_rank(const char *fn, const void *q_packed, int64_t batch, int c, const
         const int B = (int)batch, N = (int)n_ent;
         hipStream_t st = (hipStream_t)stream;
         launch_targets<T, K.value, SG.value>(qp, B, O, N, c, 0, N, obj_idx, pt, ws, st);
-        return launch_counts<T, K.value, SG.value>(qp, B, O, N, c, 0, N, pt, obj_idx, pair_slot, pair_ptr, pair_obj, 1, ranks,
-                                                   bce_rows, ws, st, fn);
+        return stable_mode(bce_rows, [&](auto mode) {
+            return launch_counts<T, K.value, SG.value, decltype(mode)>(qp, B, O, N, c, 0, N, pt, obj_idx, pair_slot, pair_ptr,
+                                                                       pair_obj, 1, ranks, bce_rows, ws, st, fn);
+        });
     });
 }
 
@@ -556,8 +514,11 @@ extern "C" int rtk_score_rank_counts_f32(const void *q_packed, int64_t batch, in
                                          const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
                                          unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
                                          size_t ws_bytes, void *stream) {
-    return rank_counts<float>("rtk_score_rank_counts_f32", q_packed, batch, c, O_local, n_local, col0, n_ent, pt, obj_idx,
-                              pair_slot, pair_ptr, pair_obj, flags, counts_out, bce_rows_out, workspace, ws_bytes, stream);
+    return stable_mode(bce_rows_out, [&](auto mode) {
+        return rank_counts<float, decltype(mode)>("rtk_score_rank_counts_f32", q_packed, batch, c, O_local, n_local, col0,
+                                                  n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, flags, counts_out,
+                                                  bce_rows_out, workspace, ws_bytes, stream);
+    });
 }
 
 extern "C" int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, int c, const void *O_local, int64_t n_local,
@@ -565,12 +526,15 @@ extern "C" int rtk_score_rank_counts_bf16(const void *q_packed, int64_t batch, i
                                           const int64_t *pair_slot, const int64_t *pair_ptr, const int64_t *pair_obj,
                                           unsigned flags, int32_t *counts_out, double *bce_rows_out, void *workspace,
                                           size_t ws_bytes, void *stream) {
-    return rank_counts<rtk_bf16>("rtk_score_rank_counts_bf16", q_packed, batch, c, (const rtk_bf16 *)O_local, n_local, col0,
-                                 n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, flags, counts_out, bce_rows_out,
-                                 workspace, ws_bytes, stream);
+    return stable_mode(bce_rows_out, [&](auto mode) {
+        return rank_counts<rtk_bf16, decltype(mode)>("rtk_score_rank_counts_bf16", q_packed, batch, c,
+                                                     (const rtk_bf16 *)O_local, n_local, col0, n_ent, pt, obj_idx, pair_slot,
+                                                     pair_ptr, pair_obj, flags, counts_out, bce_rows_out, workspace, ws_bytes,
+                                                     stream);
+    });
 }
 
-// the block layout (the tie counts use its BCE planes for the equal counts); 0 outside the covered range
+// the block layout (the Ties mode's second planes hold the equal counts); 0 outside the covered range
 extern "C" size_t rtk_score_rank_ties_workspace_bytes(int dtype, int64_t batch, int64_t n_local, int c) {
     if (batch < 0 || batch >= (1ll << 31) - 32 || n_local < 1 || n_local >= (1ll << 31) - 64 || c < 1) return 0;
     if (dtype == RTK_F32 ? (c > 16 * SW_MAX_KS_F32 || c % 4 != 0) : (dtype != RTK_BF16 || c > 16 * SW_MAX_KS_BF16)) return 0;
@@ -582,9 +546,9 @@ extern "C" int rtk_score_rank_tie_counts_f32(const void *q_packed, int64_t batch
                                              const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
                                              const int64_t *pair_obj, unsigned flags, int32_t *greater_out,
                                              int32_t *equal_out, void *workspace, size_t ws_bytes, void *stream) {
-    return rank_tie_counts<float>("rtk_score_rank_tie_counts_f32", q_packed, batch, c, O_local, n_local, col0, n_ent, pt,
-                                  obj_idx, pair_slot, pair_ptr, pair_obj, flags, greater_out, equal_out, workspace, ws_bytes,
-                                  stream);
+    return rank_counts<float, Ties>("rtk_score_rank_tie_counts_f32", q_packed, batch, c, O_local, n_local, col0, n_ent, pt,
+                                    obj_idx, pair_slot, pair_ptr, pair_obj, flags, greater_out, equal_out, workspace,
+                                    ws_bytes, stream);
 }
 
 extern "C" int rtk_score_rank_tie_counts_bf16(const void *q_packed, int64_t batch, int c, const void *O_local,
@@ -592,7 +556,7 @@ extern "C" int rtk_score_rank_tie_counts_bf16(const void *q_packed, int64_t batc
                                               const int64_t *obj_idx, const int64_t *pair_slot, const int64_t *pair_ptr,
                                               const int64_t *pair_obj, unsigned flags, int32_t *greater_out,
                                               int32_t *equal_out, void *workspace, size_t ws_bytes, void *stream) {
-    return rank_tie_counts<rtk_bf16>("rtk_score_rank_tie_counts_bf16", q_packed, batch, c, (const rtk_bf16 *)O_local, n_local,
-                                     col0, n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, flags, greater_out, equal_out,
-                                     workspace, ws_bytes, stream);
+    return rank_counts<rtk_bf16, Ties>("rtk_score_rank_tie_counts_bf16", q_packed, batch, c, (const rtk_bf16 *)O_local,
+                                       n_local, col0, n_ent, pt, obj_idx, pair_slot, pair_ptr, pair_obj, flags, greater_out,
+                                       equal_out, workspace, ws_bytes, stream);
 }

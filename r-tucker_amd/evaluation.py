@@ -23,6 +23,14 @@ from . import _lib
 from .tucker import SFTucker, Tucker
 
 
+def _resolve_device(device):
+    """``device`` as a ``torch.device``, a bare "cuda" as the current CUDA device."""
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return device
+
+
 class DeviceFilter:
     """The (subject, relation) -> known-true-objects CSR of a ``KG_dataset`` on the device."""
 
@@ -86,9 +94,7 @@ class DeviceFilter:
     @classmethod
     def of(cls, dataset, device):
         """The filter of ``dataset`` on ``device``, built once per dataset object (``evaluate()`` runs twice per epoch)."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _resolve_device(device)
         cache = dataset.__dict__.setdefault("_device_filters", {})
         if device not in cache:
             cache[device] = cls(dataset, device)
@@ -154,9 +160,7 @@ class RelationFilter:
     @classmethod
     def of(cls, dataset, device):
         """The relation filter of ``dataset`` on ``device``, built once per dataset object."""
-        device = torch.device(device)
-        if device.type == "cuda" and device.index is None:
-            device = torch.device("cuda", torch.cuda.current_device())
+        device = _resolve_device(device)
         cache = dataset.__dict__.setdefault("_relation_filters", {})
         if device not in cache:
             cache[device] = cls(dataset, device)
@@ -171,31 +175,52 @@ class _RowSlots:
         self.pair_ptr, self.pair_obj, self.slot_of_item = flt.pair_ptr, flt.pair_obj, slots
 
 
+def _score_matrix(P, shape, topk=False):
+    """The checked score matrix of a ranking call -> ``(B, n, ld, device)``: a float32 GPU matrix with unit column stride
+    (``topk``: or bfloat16, and a single column may have any stride).  ``shape``: how the caller's message names it."""
+    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dim() != 2
+            or P.dtype not in ((torch.float32, torch.bfloat16) if topk else (torch.float32,))
+            or ((P.shape[1] > 1 or not topk) and P.stride(1) != 1)):
+        raise RuntimeError(f"P must be a float32 {'or bfloat16 ' if topk else ''}{shape} GPU tensor with unit column stride")
+    return P.shape[0], P.shape[1], P.stride(0), P.device
+
+
+def _per_row(name, t, B, dev, dtype=torch.int64):
+    """``t`` as a flat contiguous ``dtype`` tensor on ``dev`` with one entry per row of P."""
+    t = torch.as_tensor(t).to(device=dev, dtype=dtype).contiguous().view(-1)
+    if t.numel() != B:
+        raise RuntimeError(f"{name} must have one entry per row of P")
+    return t
+
+
+def _csr(flt, B, dev, item_ids=None, slots=None):
+    """``(slot, pointers)`` of a call's filter: the rows' CSR slots (from ``slots``, or of the dataset items
+    ``item_ids``; the caller keeps the tensor alive) and the ``pair_slot, pair_ptr, pair_obj`` arguments of the C entries
+    -- three NULLs without ``flt``."""
+    if flt is None:
+        return None, (None, None, None)
+    if slots is None and item_ids is None:
+        raise ValueError("filtering needs the rows' filter slots: item_ids (dataset items) or slots (flt.slots_of)")
+    slot = _per_row("slots", slots if slots is not None else flt.slot_of_item[torch.as_tensor(item_ids).to(dev)], B, dev)
+    return slot, (slot.data_ptr(), flt.pair_ptr.data_ptr(), flt.pair_obj.data_ptr())
+
+
+def _stream(dev):
+    return torch.cuda.current_stream(dev).cuda_stream
+
+
 def filtered_ranks(P: torch.Tensor, obj_idx: torch.Tensor, flt: DeviceFilter = None, item_ids: torch.Tensor = None,
                    want_bce: bool = False):
     """Ranks (int32, B) of ``obj_idx`` in the rows of ``P`` after filtering; optionally the per-row BCE sums."""
     lib = _lib.load()
-    if not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2 or P.stride(1) != 1:
-        raise RuntimeError("P must be a float32 (B, N) GPU tensor with unit column stride")
-    B, N = P.shape
-    dev = P.device
-    obj = obj_idx.to(device=dev, dtype=torch.int64).contiguous().view(-1)
-    if obj.numel() != B:
-        raise RuntimeError("obj_idx must have one entry per row of P")
+    B, N, ld, dev = _score_matrix(P, "(B, N)")
+    obj = _per_row("obj_idx", obj_idx, B, dev)
     ranks = torch.empty(B, dtype=torch.int32, device=dev)
     bce = torch.empty(B, dtype=torch.float64, device=dev) if want_bce else None
-    slot = ptr = objs = None
-    if flt is not None:
-        slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-        ptr, objs = flt.pair_ptr, flt.pair_obj
+    slot, csr = _csr(flt, B, dev, item_ids)
     with torch.cuda.device(dev):
-        sp = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rtk_filtered_rank_f32(P.data_ptr(), B, N, P.stride(0), obj.data_ptr(),
-                                             slot.data_ptr() if slot is not None else None,
-                                             ptr.data_ptr() if ptr is not None else None,
-                                             objs.data_ptr() if objs is not None else None,
-                                             ranks.data_ptr(), bce.data_ptr() if want_bce else None, sp),
-                   "rtk_filtered_rank_f32")
+        _lib.check(lib.rtk_filtered_rank_f32(P.data_ptr(), B, N, ld, obj.data_ptr(), *csr, ranks.data_ptr(),
+                                             bce.data_ptr() if want_bce else None, _stream(dev)), "rtk_filtered_rank_f32")
     return (ranks, bce) if want_bce else ranks
 
 
@@ -211,44 +236,27 @@ def filtered_topk(P: torch.Tensor, k: int, flt: DeviceFilter = None, item_ids: t
     (``flt.slots_of(subject_idx, relation_idx)``; -1 = no filtering).  A row with fewer than k eligible candidates
     is padded with (-inf, -1).  ``P`` is not modified."""
     lib = _lib.load()
-    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dim() != 2 or P.dtype not in (torch.float32, torch.bfloat16)
-            or (P.shape[1] > 1 and P.stride(1) != 1)):
-        raise RuntimeError("P must be a float32 or bfloat16 (B, n) GPU tensor with unit column stride")
+    B, n, ld, dev = _score_matrix(P, "(B, n)", topk=True)
     k = int(k)
     if not 1 <= k <= 1024:
         raise ValueError(f"k = {k}: the selection takes 1 <= k <= 1024")
-    B, n = P.shape
-    dev = P.device
-
-    def per_row(name, t):
-        t = torch.as_tensor(t).to(device=dev, dtype=torch.int64).contiguous().view(-1)
-        if t.numel() != B:
-            raise RuntimeError(f"{name} must have one entry per row of P")
-        return t
-    slot = None
-    if flt is not None:
-        if slots is None and item_ids is None:
-            raise ValueError("filtering needs the rows' filter slots: item_ids (dataset items) or slots (flt.slots_of)")
-        slot = per_row("slots", slots if slots is not None else flt.slot_of_item[torch.as_tensor(item_ids).to(dev)])
-    elif slots is not None or item_ids is not None:
+    if flt is None and (slots is not None or item_ids is not None):
         raise ValueError("slots / item_ids need flt (the DeviceFilter that holds the CSR)")
-    keep = per_row("keep_idx", keep_idx) if keep_idx is not None else None
+    slot, csr = _csr(flt, B, dev, item_ids, slots)
+    keep = _per_row("keep_idx", keep_idx, B, dev) if keep_idx is not None else None
     if ids is not None:
         if (not isinstance(ids, torch.Tensor) or ids.dtype != torch.int64 or ids.device != dev
                 or tuple(ids.shape) != (B, n) or (n > 1 and ids.stride(1) != 1)):
             raise RuntimeError(f"ids must be an int64 ({B}, {n}) tensor on {dev} with unit column stride")
     values = torch.empty((B, k), dtype=torch.float32, device=dev)
     out_ids = torch.empty((B, k), dtype=torch.int64, device=dev)
-    ld = P.stride(0) if B > 1 else n
+    ld = ld if B > 1 else n
     ld_ids = (ids.stride(0) if B > 1 else n) if ids is not None else 0
     fn = lib.rtk_select_topk_bf16 if P.dtype == torch.bfloat16 else lib.rtk_select_topk_f32
     with torch.cuda.device(dev):
-        _lib.check(fn(P.data_ptr(), B, n, ld, int(col0), ids.data_ptr() if ids is not None else None, ld_ids,
-                      slot.data_ptr() if slot is not None else None,
-                      flt.pair_ptr.data_ptr() if slot is not None else None,
-                      flt.pair_obj.data_ptr() if slot is not None else None,
+        _lib.check(fn(P.data_ptr(), B, n, ld, int(col0), ids.data_ptr() if ids is not None else None, ld_ids, *csr,
                       keep.data_ptr() if keep is not None else None, k, values.data_ptr(), out_ids.data_ptr(), None, 0,
-                      torch.cuda.current_stream(dev).cuda_stream), "rtk_select_topk")
+                      _stream(dev)), "rtk_select_topk")
     return values, out_ids
 
 
@@ -256,43 +264,37 @@ def target_scores_block(P: torch.Tensor, obj_idx: torch.Tensor, col0: int) -> to
     """Scores of the queried objects that fall into this column block, -inf for the others
     (step 1 of the sharded ranking; all-reduce MAX over the ranks completes it)."""
     lib = _lib.load()
-    B, n_loc = P.shape
-    dev = P.device
-    obj = obj_idx.to(device=dev, dtype=torch.int64).contiguous().view(-1)
+    B, n_loc, ld, dev = _score_matrix(P, "(B, n_local)")
+    obj = _per_row("obj_idx", obj_idx, B, dev)
     pt = torch.empty(B, dtype=torch.float32, device=dev)
     with torch.cuda.device(dev):
-        sp = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rtk_target_scores_f32(P.data_ptr(), B, n_loc, P.stride(0), int(col0), obj.data_ptr(),
-                                             pt.data_ptr(), sp), "rtk_target_scores_f32")
+        _lib.check(lib.rtk_target_scores_f32(P.data_ptr(), B, n_loc, ld, int(col0), obj.data_ptr(), pt.data_ptr(),
+                                             _stream(dev)), "rtk_target_scores_f32")
     return pt
+
+
+def _counts_block(entry, P, obj_idx, col0, target_scores, flt, item_ids, out0, out1, skip_empty):
+    """Step 2 on a stored column block through the C entry ``entry``: the checked operands, the completed target scores
+    and the filter's CSR into two (B,) outputs allocated by ``out0`` / ``out1`` (a dtype, or None: NULL)."""
+    lib = _lib.load()
+    B, n_loc, ld, dev = _score_matrix(P, "(B, n_local)")
+    obj = _per_row("obj_idx", obj_idx, B, dev)
+    outs = [torch.empty(B, dtype=dt, device=dev) if dt is not None else None for dt in (out0, out1)]
+    slot, csr = _csr(flt, B, dev, item_ids)
+    pt = _per_row("target_scores", target_scores, B, dev, torch.float32)
+    if B > 0 or not skip_empty:                              # (the C entries refuse an empty batch)
+        with torch.cuda.device(dev):
+            _lib.check(getattr(lib, entry)(P.data_ptr(), B, n_loc, ld, int(col0), pt.data_ptr(), obj.data_ptr(), *csr,
+                                           *(o.data_ptr() if o is not None else None for o in outs), _stream(dev)), entry)
+    return outs
 
 
 def rank_counts_block(P: torch.Tensor, obj_idx: torch.Tensor, col0: int, target_scores: torch.Tensor,
                       flt: DeviceFilter = None, item_ids: torch.Tensor = None, want_bce: bool = False):
     """This column block's share of the rank count (int32, B) and, optionally, of the BCE row sums
     (step 2 of the sharded ranking; all-reduce SUM, then rank = 1 + count)."""
-    lib = _lib.load()
-    if not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2 or P.stride(1) != 1:
-        raise RuntimeError("P must be a float32 (B, n_local) GPU tensor with unit column stride")
-    B, n_loc = P.shape
-    dev = P.device
-    obj = obj_idx.to(device=dev, dtype=torch.int64).contiguous().view(-1)
-    counts = torch.empty(B, dtype=torch.int32, device=dev)
-    bce = torch.empty(B, dtype=torch.float64, device=dev) if want_bce else None
-    slot = ptr = objs = None
-    if flt is not None:
-        slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-        ptr, objs = flt.pair_ptr, flt.pair_obj
-    pt = target_scores.to(device=dev, dtype=torch.float32).contiguous()
-    with torch.cuda.device(dev):
-        sp = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rtk_filtered_rank_partial_f32(P.data_ptr(), B, n_loc, P.stride(0), int(col0), pt.data_ptr(),
-                                                     obj.data_ptr(),
-                                                     slot.data_ptr() if slot is not None else None,
-                                                     ptr.data_ptr() if ptr is not None else None,
-                                                     objs.data_ptr() if objs is not None else None,
-                                                     counts.data_ptr(), bce.data_ptr() if want_bce else None, sp),
-                   "rtk_filtered_rank_partial_f32")
+    counts, bce = _counts_block("rtk_filtered_rank_partial_f32", P, obj_idx, col0, target_scores, flt, item_ids, torch.int32,
+                                torch.float64 if want_bce else None, skip_empty=False)
     return (counts, bce) if want_bce else counts
 
 
@@ -301,48 +303,17 @@ def tie_counts_block(P: torch.Tensor, obj_idx: torch.Tensor, col0: int, target_s
     """This column block's share of the two tie counts (``rtk_filtered_tie_counts_partial_f32``) ->
     ``(greater, equal)`` int32 (B,): the columns j != t of the block with ``p'_j > p_t`` and with ``p'_j == p_t``,
     p' = the row with the query's other known-true objects set to 0.  Arguments as ``rank_counts_block``; the blocks'
-    counts add up exactly (all-reduce SUM)."""
-    lib = _lib.load()
-    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2
-            or P.stride(1) != 1):
-        raise RuntimeError("P must be a float32 (B, n_local) GPU tensor with unit column stride")
-    B, n_loc = P.shape
-    dev = P.device
-    obj = obj_idx.to(device=dev, dtype=torch.int64).contiguous().view(-1)
-    if obj.numel() != B:
-        raise RuntimeError("obj_idx must have one entry per row of P")
-    greater = torch.empty(B, dtype=torch.int32, device=dev)
-    equal = torch.empty(B, dtype=torch.int32, device=dev)
-    slot = ptr = objs = None
-    if flt is not None:
-        slot = flt.slot_of_item[item_ids.to(dev)].contiguous()
-        ptr, objs = flt.pair_ptr, flt.pair_obj
-    pt = target_scores.to(device=dev, dtype=torch.float32).contiguous()
-    if pt.numel() != B:
-        raise RuntimeError("target_scores must have one entry per row of P")
-    if B == 0:
-        return greater, equal
-    with torch.cuda.device(dev):
-        sp = torch.cuda.current_stream(dev).cuda_stream
-        _lib.check(lib.rtk_filtered_tie_counts_partial_f32(P.data_ptr(), B, n_loc, P.stride(0), int(col0), pt.data_ptr(),
-                                                           obj.data_ptr(),
-                                                           slot.data_ptr() if slot is not None else None,
-                                                           ptr.data_ptr() if ptr is not None else None,
-                                                           objs.data_ptr() if objs is not None else None,
-                                                           greater.data_ptr(), equal.data_ptr(), sp),
-                   "rtk_filtered_tie_counts_partial_f32")
-    return greater, equal
+    counts add up exactly (all-reduce SUM).  An empty batch gives empty counts."""
+    return tuple(_counts_block("rtk_filtered_tie_counts_partial_f32", P, obj_idx, col0, target_scores, flt, item_ids,
+                               torch.int32, torch.int32, skip_empty=True))
 
 
 def filtered_tie_counts(P: torch.Tensor, obj_idx: torch.Tensor, flt: DeviceFilter = None, item_ids: torch.Tensor = None):
     """The tie counts ``(greater, equal)`` (int32, B) of ``obj_idx`` in the rows of ``P`` after filtering: the whole
     matrix as the block ``col0 = 0``.  ``1 + greater <= filtered_ranks <= 1 + greater + equal``."""
-    if (not isinstance(P, torch.Tensor) or not P.is_cuda or P.dtype != torch.float32 or P.dim() != 2
-            or P.stride(1) != 1):
-        raise RuntimeError("P must be a float32 (B, N) GPU tensor with unit column stride")
-    if P.shape[0] == 0:
-        return tie_counts_block(P, obj_idx, 0, torch.empty(0, dtype=torch.float32, device=P.device), flt, item_ids)
-    return tie_counts_block(P, obj_idx, 0, target_scores_block(P, obj_idx, 0), flt, item_ids)
+    B, _, _, dev = _score_matrix(P, "(B, N)")
+    pt = target_scores_block(P, obj_idx, 0) if B > 0 else torch.empty(0, dtype=torch.float32, device=dev)
+    return tie_counts_block(P, obj_idx, 0, pt, flt, item_ids)
 
 
 _TIE_TYPES = ("optimistic", "realistic", "pessimistic")      # the order of rtk_tie_metrics_f64's accumulators
@@ -370,6 +341,31 @@ def metrics_from_ranks(ranks: torch.Tensor):
     r = ranks.to(torch.float64)
     return {"mrr": (1.0 / r).sum(), "hits@1": (ranks <= 1).sum(), "hits@3": (ranks <= 3).sum(),
             "hits@10": (ranks <= 10).sum()}
+
+
+def _eval_operands(model, device):
+    """``(core, R, S, O, sym, device)`` of an evaluation pass: the model's parameters (a symmetric model's entity matrix
+    as both S and O) and the device the pass runs on (``device`` or the parameters')."""
+    device = _resolve_device(device if device is not None else next(model.parameters()).device)
+    sym = hasattr(model, "E")
+    S = model.E.weight.data if sym else model.S.weight.data
+    return model.core.data, model.R.weight.data, S, S if sym else model.O.weight.data, sym, device
+
+
+def _add_tie_metrics(lib, greater, equal, nb, acc13, sp):
+    """acc13 += the tie-aware metric sums of ``nb`` queries (``rtk_tie_metrics_f64``; arguments are device pointers)."""
+    _lib.check(lib.rtk_tie_metrics_f64(greater, equal, nb, acc13, sp), "rtk_tie_metrics_f64")
+
+
+def _metrics(sums, n, rank_type=None):
+    """The metrics dictionary over ``n`` queries from the running sums: of the stable rank (``rtk_rank_metrics_*``'s
+    first four) or, with ``rank_type``, that type's four of ``rtk_tie_metrics_f64``'s 13 and the share of tied queries."""
+    n = max(n, 1)
+    k = 0 if rank_type is None else 4 * _TIE_TYPES.index(rank_type)
+    out = {name: sums[k + i] / n for i, name in enumerate(("mrr", "hits@1", "hits@3", "hits@10"))}
+    if rank_type is not None:
+        out["tied"] = sums[12] / n
+    return out
 
 
 class _EvalPlan:
@@ -417,15 +413,9 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
     from . import ops
     if rank_type is not None:
         _check_tie_type(rank_type)
-    device = torch.device(device) if device is not None else next(model.parameters()).device
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    core, R, S, O, _, device = _eval_operands(model, device)
     flt = flt or DeviceFilter.of(dataset, device)
     model.eval()          # train.py:96; also drops the relation-table cache: the tables are rebuilt once, below
-    sym = hasattr(model, "E")
-    core, R = model.core.data, model.R.weight.data
-    S = model.E.weight.data if sym else model.S.weight.data
-    O = S if sym else model.O.weight.data
     n = len(dataset)
     a, b, c = core.shape
     if (b != c or core.dtype not in (torch.float32, torch.bfloat16) or not ops._packed_stage2(c, exact=False)
@@ -473,23 +463,12 @@ def evaluate(model, dataset, batch_size=512, device=None, flt: DeviceFilter = No
                 _lib.check(lib.rtk_target_scores_f32(P, nb, N, plan.ld, 0, op + o8, ptp, sp), "rtk_target_scores_f32")
                 _lib.check(lib.rtk_filtered_tie_counts_partial_f32(P, nb, N, plan.ld, 0, ptp, op + o8, slp + o8, ptr, objs,
                                                                    gtp, eqp, sp), "rtk_filtered_tie_counts_partial_f32")
-                _lib.check(lib.rtk_tie_metrics_f64(gtp, eqp, nb, tap, sp), "rtk_tie_metrics_f64")
+                _add_tie_metrics(lib, gtp, eqp, nb, tap, sp)
             n_batches += 1
     acc = plan.acc.cpu().tolist()
-    tie_sums = tie_acc.cpu().tolist() if rank_type is not None else None
+    sums = tie_acc.cpu().tolist() if rank_type is not None else acc
     ops.check_device_errors(device)
-    if rank_type is not None:
-        return _tie_metrics(tie_sums, rank_type, n), acc[4] / max(n_batches, 1)
-    sums = {"mrr": acc[0] / n, "hits@1": acc[1] / n, "hits@3": acc[2] / n, "hits@10": acc[3] / n}
-    return sums, acc[4] / max(n_batches, 1)
-
-
-def _tie_metrics(acc13, rank_type, n):
-    """The metrics dictionary of one rank type from rtk_tie_metrics_f64's 13 running sums over ``n`` queries."""
-    k = 4 * _TIE_TYPES.index(rank_type)
-    n = max(n, 1)
-    return {"mrr": acc13[k] / n, "hits@1": acc13[k + 1] / n, "hits@3": acc13[k + 2] / n, "hits@10": acc13[k + 3] / n,
-            "tied": acc13[12] / n}
+    return _metrics(sums, n, rank_type), acc[4] / max(n_batches, 1)
 
 
 @torch.no_grad()
@@ -505,7 +484,6 @@ def _evaluate_generic(model, dataset, batch_size, device, flt, rank_type=None):
     lib = _lib.load()
     acc = torch.zeros(5, dtype=torch.float64, device=device)   # running sums on the device: one sync at the end
     tie_acc = torch.zeros(13, dtype=torch.float64, device=device) if rank_type is not None else None
-    loss_terms = 0
     n_batches = 0
     # out-of-range ids: checked once, at the loop's own synchronisation point below (reference: IndexError)
     with index_check("deferred"):
@@ -519,19 +497,15 @@ def _evaluate_generic(model, dataset, batch_size, device, flt, rank_type=None):
             bce.mul_(1.0 / (P.shape[0] * P.shape[1]))
             with torch.cuda.device(device):
                 _lib.check(lib.rtk_rank_metrics_f64(ranks.data_ptr(), bce.data_ptr(), hi - lo, acc.data_ptr(),
-                                                    torch.cuda.current_stream(device).cuda_stream), "rtk_rank_metrics_f64")
+                                                    _stream(device)), "rtk_rank_metrics_f64")
                 if rank_type is not None:
                     greater, equal = filtered_tie_counts(P, f[:, 2], flt, ids)
-                    _lib.check(lib.rtk_tie_metrics_f64(greater.data_ptr(), equal.data_ptr(), hi - lo, tie_acc.data_ptr(),
-                                                       torch.cuda.current_stream(device).cuda_stream), "rtk_tie_metrics_f64")
+                    _add_tie_metrics(lib, greater.data_ptr(), equal.data_ptr(), hi - lo, tie_acc.data_ptr(), _stream(device))
             n_batches += 1
     acc = acc.cpu().tolist()
-    tie_sums = tie_acc.cpu().tolist() if rank_type is not None else None
+    sums = tie_acc.cpu().tolist() if rank_type is not None else acc
     check_device_errors(device)
-    if rank_type is not None:
-        return _tie_metrics(tie_sums, rank_type, n), acc[4] / n_batches
-    sums = {"mrr": acc[0] / n, "hits@1": acc[1] / n, "hits@3": acc[2] / n, "hits@10": acc[3] / n}
-    return sums, acc[4] / n_batches
+    return _metrics(sums, n, rank_type), acc[4] / n_batches
 
 
 @torch.no_grad()
@@ -555,17 +529,11 @@ def evaluate_relations(model, dataset, batch_size=512, device=None, flt: Relatio
     from . import ops
     if rank_type is not None:
         _check_tie_type(rank_type)
-    device = torch.device(device) if device is not None else next(model.parameters()).device
-    if device.type == "cuda" and device.index is None:
-        device = torch.device("cuda", torch.cuda.current_device())
+    core, R, S, O, _, device = _eval_operands(model, device)
     flt = flt or RelationFilter.of(dataset, device)
     if flt.obj is None:
         raise RuntimeError("evaluate_relations needs a test-mode dataset: its items are (subject, relation, object) triples")
     model.eval()
-    sym = hasattr(model, "E")
-    core, R = model.core.data, model.R.weight.data
-    S = model.E.weight.data if sym else model.S.weight.data
-    O = S if sym else model.O.weight.data
     n = len(dataset)
     lib = _lib.load()
     acc = torch.zeros(4, dtype=torch.float64, device=device)
@@ -581,11 +549,7 @@ def evaluate_relations(model, dataset, batch_size=512, device=None, flt: Relatio
             else:
                 greater, equal = filtered_tie_counts(P, flt.rel[lo:hi], flt, ids)
                 with torch.cuda.device(device):
-                    _lib.check(lib.rtk_tie_metrics_f64(greater.data_ptr(), equal.data_ptr(), hi - lo, tie_acc.data_ptr(),
-                                                       torch.cuda.current_stream(device).cuda_stream), "rtk_tie_metrics_f64")
+                    _add_tie_metrics(lib, greater.data_ptr(), equal.data_ptr(), hi - lo, tie_acc.data_ptr(), _stream(device))
     sums = (acc if rank_type is None else tie_acc).cpu().tolist()
     ops.check_device_errors(device)
-    if rank_type is not None:
-        return _tie_metrics(sums, rank_type, n), None
-    n = max(n, 1)
-    return {"mrr": sums[0] / n, "hits@1": sums[1] / n, "hits@3": sums[2] / n, "hits@10": sums[3] / n}, None
+    return _metrics(sums, n, rank_type), None

@@ -1285,6 +1285,24 @@ def topk_1vN(core, R, S, O, subject_idx, relation_idx, k, flt=None, keep_idx=Non
     return values, ids
 
 
+def _rank_operands(core, R, S, O, subject_idx, relation_idx, object_idx, flt):
+    """``(op, t, slots)`` of a ranking call on the whole entity range: the checked operands, the queries' object ids and
+    their filter slots (None without ``flt`` or without queries)."""
+    nt, nh = torch.as_tensor(object_idx).numel(), torch.as_tensor(subject_idx).numel()
+    if nt != nh:
+        raise RuntimeError(f"object_idx has {nt} entries for {nh} queries")
+    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    t = _idx("object_idx", object_idx, op.dev)
+    return op, t, flt.slots_of(op.h, op.r) if flt is not None and op.B else None
+
+
+def _packed_queries(op, sp, tables):
+    """Stage 1 of ``op``'s queries on stream ``sp`` into the device's packed-plane buffer."""
+    qp = _packed_buffer(op.dev, sp, _size("rtk_packed_query_bytes", op.dcode, op.B, op.c))
+    _stage1(op, sp, tables, None, qp)
+    return qp
+
+
 @torch.no_grad()
 def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, want_bce=False, sigmoid_mode=None,
              tables=None, rank_type="stable"):
@@ -1308,22 +1326,16 @@ def rank_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None, wan
         greater, equal = rank_ties_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=flt,
                                        sigmoid_mode=sigmoid_mode, tables=tables)
         return ranks_from_tie_counts(greater, equal, rank_type)
-    nt, nh = torch.as_tensor(object_idx).numel(), torch.as_tensor(subject_idx).numel()
-    if nt != nh:
-        raise RuntimeError(f"object_idx has {nt} entries for {nh} queries")
-    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    op, t, slots = _rank_operands(core, R, S, O, subject_idx, relation_idx, object_idx, flt)
     B, N, dev = op.B, op.O.shape[0], op.dev
-    t = _idx("object_idx", object_idx, dev)
     flags = _score_flags(True, sigmoid_mode, torch.float32, op.bf16)
     ranks = torch.empty(B, dtype=torch.int32, device=dev)
     bce = torch.empty(B, dtype=torch.float64, device=dev) if want_bce else None
     if B == 0:
         return (ranks, bce) if want_bce else ranks
-    slots = flt.slots_of(op.h, op.r) if flt is not None else None
     with torch.cuda.device(dev):
         sp = _stream_ptr(dev)
-        qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.c))
-        _stage1(op, sp, tables, None, qp)
+        qp = _packed_queries(op, sp, tables)
         ws = _workspace(dev, sp, _size("rtk_score_rank_workspace_bytes", op.dcode, B, N, op.c))
         _lib.check(_entry("rtk_score_rank", op.bf16)(
             qp.data_ptr(), B, op.c, op.O.data_ptr(), N, t.data_ptr(),
@@ -1490,19 +1502,12 @@ def rank_ties_1vN(core, R, S, O, subject_idx, relation_idx, object_idx, flt=None
     ``rank_tie_counts_block_1vN``, at ``col0 = 0``).  ``equal > 0`` marks a query whose rank the tie rule decides;
     ``ranks_from_tie_counts`` turns the counts into optimistic, realistic or pessimistic ranks.  Operands, filter and
     error policy as ``rank_1vN``."""
-    nt, nh = torch.as_tensor(object_idx).numel(), torch.as_tensor(subject_idx).numel()
-    if nt != nh:
-        raise RuntimeError(f"object_idx has {nt} entries for {nh} queries")
-    op = _Operands(core, R, S, O, subject_idx, relation_idx)
+    op, t, slots = _rank_operands(core, R, S, O, subject_idx, relation_idx, object_idx, flt)
     B, N, dev = op.B, op.O.shape[0], op.dev
-    t = _idx("object_idx", object_idx, dev)
     if B == 0:
         return torch.empty(0, dtype=torch.int32, device=dev), torch.empty(0, dtype=torch.int32, device=dev)
-    slots = flt.slots_of(op.h, op.r) if flt is not None else None
     with torch.cuda.device(dev):
-        sp = _stream_ptr(dev)
-        qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, op.c))
-        _stage1(op, sp, tables, None, qp)
+        qp = _packed_queries(op, _stream_ptr(dev), tables)
         pt = rank_targets_block(qp, B, op.O, 0, N, t, sigmoid_mode=sigmoid_mode)
         return rank_tie_counts_block_1vN(qp, B, op.O, 0, N, pt, t, flt=flt, slots=slots, sigmoid_mode=sigmoid_mode)
 
