@@ -19,6 +19,8 @@ from __future__ import annotations
 
 import torch
 
+from ..ops import rank_1vN, score_1vN, score_candidates, score_triples, topk_1vN
+
 
 class TablesCacheMixin:
     cache_tables = True
@@ -58,13 +60,60 @@ class TablesCacheMixin:
         return self.__dict__["_tables"]
 
 
-class RelationQueriesMixin:
-    """Relation prediction, (h, ?, t), for both model flavours: the model's own parameters through
-    ``ops.score_relations`` (the symmetric model passes ``E`` as S and O)."""
+class ObjectQueriesMixin:
+    """Object prediction, (h, r, ?), for both model flavours, written once on two hooks of the flavour:
+    ``_operands_of(T)`` -> ``(core, R, S, O)`` of a Tucker container (sizes, dtype and device come from T, never from
+    ``self.rank``: during training T is the doubled-rank tangent-space construct) and
+    ``_relation_operands()`` -> the same four of the model's own parameters.  The symmetric model gives its one entity
+    matrix as both S and O; autograd sums the two gradients.  In eval mode the relation tables are cached."""
 
-    def _relation_operands(self):
-        E = self.E.weight if hasattr(self, "E") else None
-        return self.core, self.R.weight, (E if E is not None else self.S.weight), (E if E is not None else self.O.weight)
+    def forward(self, subject_idx, relation_idx):
+        def score_fn(T):
+            core, R, S, O = self._operands_of(T)
+            return score_1vN(core, R, S, O, subject_idx, relation_idx, tables=self._cached_tables(core, R))
+
+        return score_fn
+
+    def score_candidates(self, subject_idx, relation_idx, candidates):
+        """``score_fn(T)`` giving the (B, K) scores of each query against its own candidate entities
+        (``ops.score_candidates``; ``candidates`` int64 (B, K) on the device)."""
+        def score_fn(T):
+            core, R, S, O = self._operands_of(T)
+            return score_candidates(core, R, S, O, subject_idx, relation_idx, candidates, tables=self._cached_tables(core, R))
+
+        return score_fn
+
+    def score_triples(self, subject_idx, relation_idx, object_idx):
+        """``score_fn(T)`` giving the (B,) scores of the triples (h, r, t) (``ops.score_triples``)."""
+        def score_fn(T):
+            core, R, S, O = self._operands_of(T)
+            return score_triples(core, R, S, O, subject_idx, relation_idx, object_idx, tables=self._cached_tables(core, R))
+
+        return score_fn
+
+    def _own(self, fn, *queries, tables=None, **kw):
+        core, R, S, O = self._relation_operands()
+        return fn(core, R, S, O, *queries, tables=self._cached_tables(core, R) if tables is None else tables, **kw)
+
+    @torch.no_grad()
+    def predict(self, subject_idx, relation_idx, k=10, flt=None, **kw):
+        """The ``k`` most likely objects of each ``(subject, relation, ?)`` query, best first: ``(values, ids)``
+        (``ops.topk_1vN``; ``flt``: a ``DeviceFilter`` whose known-true objects are left out).  In eval mode the
+        relation tables are built once and reused, as by the scoring closure.  Keywords go to ``ops.topk_1vN``:
+        ``matrix_free=True`` selects without storing any scores."""
+        return self._own(topk_1vN, subject_idx, relation_idx, k, flt=flt, **kw)
+
+    @torch.no_grad()
+    def rank_objects(self, subject_idx, relation_idx, object_idx, flt=None, **kw):
+        """Filtered rank of each ``(subject, relation, object)`` query against every entity (``ops.rank_1vN``;
+        ``want_bce=True`` also returns the BCE row sums).  Relation tables as in ``predict``.  (``self.rank`` is the
+        Tucker rank, as in the reference, hence the name.)"""
+        return self._own(rank_1vN, subject_idx, relation_idx, object_idx, flt=flt, **kw)
+
+
+class RelationQueriesMixin:
+    """Relation prediction, (h, ?, t), for both model flavours: the model's own parameters (the flavour's
+    ``_relation_operands()``) through ``ops.score_relations``."""
 
     def relation_logits(self, subject_idx, object_idx):
         """Logits ``(B, n_rel)`` of every relation for each ``(subject, ?, object)`` query, differentiable in the model's

@@ -11,6 +11,7 @@ dv) is device-side torch ops.  Nothing leaves the GPU.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 import os
 
@@ -88,6 +89,40 @@ def _dtype_code(bf16):
 def _entry(name, bf16):
     """The bf16 or the f32 form of a C-ABI entry point (``name_bf16`` / ``name_f32``)."""
     return getattr(_lib.load(), name + ("_bf16" if bf16 else "_f32"))
+
+
+def _ld(t):
+    """The row pitch of a (rows, cols) matrix as the C ABI takes it: its row stride, or cols for at most one row."""
+    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
+
+
+def _wants_grad(*tensors):
+    """Whether autograd is recording and one of ``tensors`` asks for a gradient."""
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
+
+
+def _f32(*operands):
+    """The fp32 operands a backward computes with: bf16 operands (they share one dtype) upcast, fp32 ones as they are."""
+    return operands if operands[0].dtype == torch.float32 else tuple(t.float() for t in operands)
+
+
+def _grads_like(grads, dtype):
+    """Gradients computed in fp32, returned in the operands' ``dtype`` (None stays None)."""
+    return tuple(grads) if dtype == torch.float32 else tuple(None if g is None else g.to(dtype) for g in grads)
+
+
+def _zero_batch_grads(ctx):
+    """The backward of an empty batch (core, R, S, O saved first): zero gradients of each operand's shape and dtype for
+    the operands that want one, nothing launched."""
+    needs = ctx.needs_input_grad
+    return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * (len(needs) - 4)
+
+
+def _spend(ctx, who, stored):
+    """One backward per forward of a stored-matrix loss: its backward overwrites the saved matrix."""
+    if getattr(ctx, "spent", False):
+        raise RuntimeError(f"{who}: backward called twice (the saved {stored} are overwritten by the first pass)")
+    ctx.spent = True
 
 
 class _Operands:
@@ -284,7 +319,7 @@ def _stage2(bf16, sp, v, qp, O, out, flags):
     """Stage 2: the scores ``out`` (B, N) against ``O`` from the packed planes ``qp``, or, when there are none, from
     ``v`` (``rtk_score_f32``, which takes the sigmoid flag alone)."""
     B, N = out.shape
-    ld = out.stride(0) if B > 1 else N
+    ld = _ld(out)
     if qp is not None:
         _lib.check(_entry("rtk_score_packed", bf16)(qp.data_ptr(), B, O.shape[1], O.data_ptr(), N, out.data_ptr(), ld,
                                                     flags, sp), "rtk_score_packed")
@@ -335,7 +370,7 @@ def _forward(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, want_v, s
             ws = op.workspace(sp)
             _lib.check(_entry("rtk_score_1vN", op.bf16)(
                 op.core.data_ptr(), op.a, op.b, op.c, op.R.data_ptr(), op.R.shape[0], op.S.data_ptr(), op.S.shape[0],
-                op.O.data_ptr(), N, op.r.data_ptr(), op.h.data_ptr(), B, out.data_ptr(), out.stride(0) if B > 1 else N,
+                op.O.data_ptr(), N, op.r.data_ptr(), op.h.data_ptr(), B, out.data_ptr(), _ld(out),
                 flags | (_lib.RTK_SCORE_EXACT_F32 if exact else 0), ws.data_ptr(), ws.numel(), sp), "rtk_score_1vN")
         else:
             # two calls: the fp32 query vectors are kept for backward, or stage 1 reads the relation tables
@@ -358,13 +393,11 @@ class _Score1vN(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         core, R, S, O, h, r, v, out = ctx.saved_tensors
-        pdt = core.dtype                      # bf16 operands: gradients computed in fp32, returned in bf16
-        if pdt != torch.float32:
-            core, R, S, O = core.float(), R.float(), S.float(), O.float()
+        B, N = out.shape
+        if B == 0:
+            return _zero_batch_grads(ctx)
         lib = _lib.load()
         dev = out.device
-        B, N = out.shape
-        c = O.shape[1]
         grad_out = grad_out.contiguous().float()
         with torch.cuda.device(dev):
             sp = _stream_ptr(dev)
@@ -374,12 +407,11 @@ class _Score1vN(torch.autograd.Function):
                            "rtk_sigmoid_grad_f32")
             elif ctx.sigmoid:    # dZ = dP * P * (1 - P)   (HIP), written on 128-byte aligned rows for the GEMMs
                 dZ = alloc_scores(B, N, dev)
-                _lib.check(lib.rtk_sigmoid_grad_rows_f32(grad_out.data_ptr(), N, out.data_ptr(), out.stride(0) if B > 1 else N,
-                                                         dZ.data_ptr(), dZ.stride(0) if B > 1 else N, B, N, sp),
-                           "rtk_sigmoid_grad_rows_f32")
+                _lib.check(lib.rtk_sigmoid_grad_rows_f32(grad_out.data_ptr(), N, out.data_ptr(), _ld(out), dZ.data_ptr(), _ld(dZ),
+                                                         B, N, sp), "rtk_sigmoid_grad_rows_f32")
             else:
                 dZ = grad_out
-        return _grads_from_dZ(core, R, S, O, h, r, v, dZ, ctx.needs_input_grad, pdt) + (None,) * 5
+        return _grads_from_dZ(core, R, S, O, h, r, v, dZ, ctx.needs_input_grad) + (None,) * 5
 
 
 def _splits_for(M, N, K):
@@ -388,10 +420,10 @@ def _splits_for(M, N, K):
     return int(max(1, min(64, 512 // max(tiles, 1), K // 512)))
 
 
-def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, pdt, dz_bound=None, scale=None):
-    """(g_core, g_R, g_S, g_O) from dZ = d loss / d logits (B, N) fp32 and the saved fp32 query vectors,
-    all in HIP kernels with a fixed summation order (bit-identical from run to run): dO = dZ^T v and
-    dv = dZ O (split-K slabs added in chunk order) on the split-fp16 MFMA path of the forward
+def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, dz_bound=None, scale=None):
+    """(g_core, g_R, g_S, g_O) from dZ = d loss / d logits (B, N) fp32, the operands as the forward saved them (bf16
+    ones: computed in fp32, returned in bf16) and the saved fp32 query vectors, all in HIP kernels with a fixed
+    summation order (bit-identical from run to run): dO = dZ^T v and dv = dZ O (split-K slabs added in chunk order) on the split-fp16 MFMA path of the forward
     (``BACKWARD_GEMM = "f32"`` / ``R_TUCKER_AMD_BWD_GEMM=f32``: the exact fp32 MFMA GEMM), then the stage-1
     backward ``rtk_query_vectors_bwd_f32`` (two more GEMMs and a deterministic row scatter).  ``dz_bound``: a
     one-element device tensor >= max|dZ| when the caller knows one (the BCE gradient does); otherwise one
@@ -401,9 +433,10 @@ def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, pdt, dz_bound=None, scale=
     lib = _lib.load()
     dev = dZ.device
     B, N = dZ.shape
-    ldz = dZ.stride(0) if B > 1 else N      # dZ may be the (B, N) view of a padded buffer (bce_loss_1vN)
+    ldz = _ld(dZ)                           # dZ may be the (B, N) view of a padded buffer (bce_loss_1vN)
     a, b, c = core.shape
-    core, R, S, Of = core.contiguous(), R.contiguous(), S.contiguous(), O.contiguous()
+    pdt = core.dtype
+    core, R, S, Of = (t.contiguous() for t in _f32(core, R, S, O))
     gO = gcore = gR = gS = None
     sf16 = BACKWARD_GEMM != "f32"
     with torch.cuda.device(dev):
@@ -447,10 +480,8 @@ def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, pdt, dz_bound=None, scale=
             if scale is not None:
                 dv = dv * scale.to(device=dev, dtype=torch.float32).reshape(1)
             gcore, gR, gS = _stage1_backward(core, R, S, h, r, dv, needs)
-    if pdt != torch.float32:
-        gcore, gR, gS, gO = [g.to(pdt) if g is not None else None for g in (gcore, gR, gS, gO)]
     # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
-    return gcore, gR, gS, gO
+    return _grads_like((gcore, gR, gS, gO), pdt)
 
 
 class _GramTN(torch.autograd.Function):
@@ -494,6 +525,54 @@ def gram_tn(A, B):
     return A.transpose(0, 1) @ B
 
 
+# What the two losses on a stored (B, N) matrix differ in: the public name, what the score kernel stores (with or without
+# the logistic), the entries of the row sums and of the in-place gradient, and ``softmax``: the mean is taken over the B
+# rows (not the B N entries), whose log-sum-exp the rows entry hands to the gradient entry.
+_StoredLoss = collections.namedtuple("_StoredLoss", "who stored sigmoid rows grad softmax")
+_STORED_BCE = _StoredLoss("bce_loss_1vN", "scores", True, "rtk_bce_rows_f32", "rtk_bce_grad_f32", False)
+_STORED_CE = _StoredLoss("ce_loss_1vN", "logits", False, "rtk_ce_rows_f32", "rtk_ce_grad_f32", True)
+
+
+def _stored_loss_forward(ctx, kind, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps):
+    """The matrix (scores or logits) on aligned rows -- it never leaves the function pair --, its row sums, their mean."""
+    ctx.kind, ctx.eps, ctx.B = kind, float(eps), int(subject_idx.numel())
+    if ctx.B == 0:
+        ctx.save_for_backward(core, R, S, O)
+        return torch.zeros((), dtype=torch.float32, device=core.device)
+    M, v, op = _forward(core, R, S, O, subject_idx, relation_idx, kind.sigmoid, False, want_v=True, padded=True)
+    dev = M.device
+    B, N = M.shape
+    ctx.count = B if kind.softmax else B * N
+    ctx.ld = _ld(M) if kind.softmax else M.stride(0)      # (the BCE pair has always been given the buffer's pitch at B = 1 too)
+    rows = torch.empty(B, dtype=torch.float64, device=dev)
+    lse = (torch.empty(B, dtype=torch.float32, device=dev),) if kind.softmax else ()
+    with torch.cuda.device(dev):
+        _lib.check(getattr(_lib.load(), kind.rows)(M.data_ptr(), B, N, ctx.ld, pair_slot.data_ptr(), pair_ptr.data_ptr(),
+                                                   pair_obj.data_ptr(), ctx.eps, rows.data_ptr(),
+                                                   *(t.data_ptr() for t in lse), _stream_ptr(dev)), kind.rows)
+    ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, M, pair_slot, pair_ptr, pair_obj, *lse)
+    return (rows.sum() / ctx.count).to(torch.float32)
+
+
+def _stored_loss_backward(ctx, grad_loss):
+    """In place ``M <- d loss / d logits`` (the saved matrix is spent), then the gradient tail."""
+    if ctx.B == 0:
+        return _zero_batch_grads(ctx)
+    core, R, S, O, h, r, v, M, pair_slot, pair_ptr, pair_obj, *lse = ctx.saved_tensors
+    kind, norm = ctx.kind, 1.0 / ctx.count
+    _spend(ctx, kind.who, kind.stored)
+    dev = M.device
+    B, N = M.shape
+    g = grad_loss.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
+    with torch.cuda.device(dev):
+        # BCE: M <- (P - y) g / (B N); CE: M <- (w softmax - y) g / B
+        _lib.check(getattr(_lib.load(), kind.grad)(M.data_ptr(), B, N, ctx.ld, pair_slot.data_ptr(), pair_ptr.data_ptr(),
+                                                   pair_obj.data_ptr(), ctx.eps, *(t.data_ptr() for t in lse), g.data_ptr(),
+                                                   norm, _stream_ptr(dev)), kind.grad)
+    # |dZ| <= |g| norm (|P - y| <= 1, |w softmax - y| <= 1): the operand bound of the split-fp16 GEMMs, no pass over dZ
+    return _grads_from_dZ(core, R, S, O, h, r, v, M, ctx.needs_input_grad, dz_bound=g.abs() * norm) + (None,) * 6
+
+
 class _BceLoss1vN(torch.autograd.Function):
     """mean BCE(sigmoid(logits), smoothed multi-hot targets) with the targets given as a CSR."""
 
@@ -504,19 +583,8 @@ class _BceLoss1vN(torch.autograd.Function):
                 and core.shape[1] == core.shape[2] and subject_idx.numel() > 0):
             return _BceLoss1vN._forward_fused(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj,
                                               float(label_smoothing))
-        # the scores never leave this function pair: aligned rows for them too
-        P, v, op = _forward(core, R, S, O, subject_idx, relation_idx, True, False, want_v=True, padded=True)
-        lib = _lib.load()
-        dev = P.device
-        B, N = P.shape
-        rows = torch.empty(B, dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.rtk_bce_rows_f32(P.data_ptr(), B, N, P.stride(0), pair_slot.data_ptr(), pair_ptr.data_ptr(),
-                                            pair_obj.data_ptr(), float(label_smoothing), rows.data_ptr(), _stream_ptr(dev)),
-                       "rtk_bce_rows_f32")
-        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, P, pair_slot, pair_ptr, pair_obj)
-        ctx.eps = float(label_smoothing)
-        return (rows.sum() / (B * N)).to(torch.float32)
+        return _stored_loss_forward(ctx, _STORED_BCE, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj,
+                                    label_smoothing)
 
     @staticmethod
     def _forward_fused(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, eps):
@@ -530,7 +598,7 @@ class _BceLoss1vN(torch.autograd.Function):
         X = alloc_scores(B, N, dev)
         partials = torch.empty(lib.rtk_score_bce_partials(), dtype=torch.float64, device=dev)
         rows_pos = torch.empty(4 * B, dtype=torch.float64, device=dev)      # four partial sums per row
-        ld = X.stride(0) if B > 1 else N
+        ld = _ld(X)
         with torch.cuda.device(dev):
             sp = _stream_ptr(dev)
             qp = _packed_buffer(dev, sp, _size("rtk_packed_query_bytes", op.dcode, B, c))
@@ -547,31 +615,15 @@ class _BceLoss1vN(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_loss):
-        core, R, S, O, h, r, v, P, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
-        if ctx.fused:
-            B, N = P.shape
-            g = grad_loss.to(device=P.device, dtype=torch.float32).reshape(1) * (1.0 / (B * N))
-            # X = (p - y) unscaled, |X| <= 1: the GEMMs' operand bound; g / (B N) rides on the small operands
-            return _grads_from_dZ(core, R, S, O, h, r, v, P, ctx.needs_input_grad, core.dtype,
-                                  dz_bound=torch.ones(1, dtype=torch.float32, device=P.device), scale=g) + (None,) * 6
-        if getattr(ctx, "spent", False):
-            raise RuntimeError("bce_loss_1vN: backward called twice (the saved scores are overwritten by the first pass)")
-        ctx.spent = True
-        pdt = core.dtype
-        if pdt != torch.float32:
-            core, R, S, O = core.float(), R.float(), S.float(), O.float()
-        lib = _lib.load()
-        dev = P.device
-        B, N = P.shape
-        g = grad_loss.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
-        with torch.cuda.device(dev):
-            # in place: P <- (P - y) * g / (B * N) = d loss / d logits  (the saved scores are spent)
-            _lib.check(lib.rtk_bce_grad_f32(P.data_ptr(), B, N, P.stride(0), pair_slot.data_ptr(), pair_ptr.data_ptr(),
-                                            pair_obj.data_ptr(), ctx.eps, g.data_ptr(), 1.0 / (B * N), _stream_ptr(dev)),
-                       "rtk_bce_grad_f32")
-        # |dZ| = |P - y| |g| / (B N) <= |g| / (B N): the operand bound of the split-fp16 GEMMs, no pass over dZ
-        return _grads_from_dZ(core, R, S, O, h, r, v, P, ctx.needs_input_grad, pdt,
-                              dz_bound=g.abs() * (1.0 / (B * N))) + (None,) * 6
+        if not ctx.fused:
+            return _stored_loss_backward(ctx, grad_loss)
+        core, R, S, O, h, r, v, X = ctx.saved_tensors[:8]
+        B, N = X.shape
+        g = grad_loss.to(device=X.device, dtype=torch.float32).reshape(1) * (1.0 / (B * N))
+        # X = (p - y) unscaled, |X| <= 1: the GEMMs' operand bound; g / (B N) rides on the small operands
+        return _grads_from_dZ(core, R, S, O, h, r, v, X, ctx.needs_input_grad,
+                              dz_bound=torch.ones(1, dtype=torch.float32, device=X.device), scale=g) + (None,) * 6
+
 
 # Largest object rank of the matrix-free loss (rtk_bce_stream_*: one wave keeps a whole row of the dv / gO accumulator).
 _STREAM_MAX_C = 208
@@ -700,12 +752,6 @@ def _block_enter(ctx, steps, core, R, S, O_loc, subject_idx, relation_idx, eps, 
     return operands, torch.zeros((), dtype=ctx.ldt, device=core.device)
 
 
-def _zero_batch_grads(ctx):
-    """The backward of an empty batch (core, R, S, O saved): zero gradients for the operands that want one."""
-    needs = ctx.needs_input_grad
-    return tuple(torch.zeros_like(t) if n else None for t, n in zip(ctx.saved_tensors, needs[:4])) + (None,) * (len(needs) - 4)
-
-
 def _finish_dv(ctx, dv, g, needs):
     """``(g_core, g_R, g_S)`` from a block's unscaled dv: dv, (B, c), never gS, (n_ent, b), is summed over the ranks (on
     a copy where it is the forward's saved share, which stays as it is), then ``g`` and the (linear) stage-1 backward."""
@@ -768,7 +814,7 @@ def _block_loss(steps, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx
                 sigmoid_mode, max_pos, all_reduce, who="bce_loss_block_1vN"):
     slot, max_pos = _csr_slots(flt, item_ids, core.device, max_pos)
     # dv (the second tile product of sweep 1) only when a gradient of core, R or S can be asked for
-    want_dv = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S))
+    want_dv = _wants_grad(core, R, S)
     return _BceLossBlock.apply(core, R, S, O_loc, subject_idx, relation_idx, slot, flt.pair_ptr, flt.pair_obj,
                                float(label_smoothing), sigmoid_mode, max_pos, want_dv, int(col0), int(n_ent),
                                all_reduce, steps, who)
@@ -804,45 +850,10 @@ class _CeLoss1vN(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj, label_smoothing):
-        ctx.B = B = int(subject_idx.numel())
-        ctx.eps = float(label_smoothing)
-        if B == 0:
-            ctx.save_for_backward(core, R, S, O)
-            return torch.zeros((), dtype=torch.float32, device=core.device)
-        # the logits never leave this function pair: aligned rows for them
-        Z, v, op = _forward(core, R, S, O, subject_idx, relation_idx, False, False, want_v=True, padded=True)
-        lib = _lib.load()
-        dev = Z.device
-        N = Z.shape[1]
-        rows = torch.empty(B, dtype=torch.float64, device=dev)
-        lse = torch.empty(B, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.rtk_ce_rows_f32(Z.data_ptr(), B, N, Z.stride(0) if B > 1 else N, pair_slot.data_ptr(),
-                                           pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, rows.data_ptr(), lse.data_ptr(),
-                                           _stream_ptr(dev)), "rtk_ce_rows_f32")
-        ctx.save_for_backward(op.core, op.R, op.S, op.O, op.h, op.r, v, Z, lse, pair_slot, pair_ptr, pair_obj)
-        return (rows.sum() / B).to(torch.float32)
+        return _stored_loss_forward(ctx, _STORED_CE, core, R, S, O, subject_idx, relation_idx, pair_slot, pair_ptr, pair_obj,
+                                    label_smoothing)
 
-    @staticmethod
-    def backward(ctx, grad_loss):
-        needs = ctx.needs_input_grad
-        if ctx.B == 0:
-            return _zero_batch_grads(ctx)
-        core, R, S, O, h, r, v, Z, lse, pair_slot, pair_ptr, pair_obj = ctx.saved_tensors
-        if getattr(ctx, "spent", False):
-            raise RuntimeError("ce_loss_1vN: backward called twice (the saved logits are overwritten by the first pass)")
-        ctx.spent = True
-        lib = _lib.load()
-        dev = Z.device
-        B, N = Z.shape
-        g = grad_loss.to(device=dev, dtype=torch.float32).reshape(1).contiguous()
-        with torch.cuda.device(dev):
-            # in place: Z <- (w softmax - y) * g / B = d loss / d logits  (the saved logits are spent)
-            _lib.check(lib.rtk_ce_grad_f32(Z.data_ptr(), B, N, Z.stride(0) if B > 1 else N, pair_slot.data_ptr(),
-                                           pair_ptr.data_ptr(), pair_obj.data_ptr(), ctx.eps, lse.data_ptr(), g.data_ptr(),
-                                           1.0 / B, _stream_ptr(dev)), "rtk_ce_grad_f32")
-        # |dZ| = |w softmax - y| |g| / B <= |g| / B: the operand bound of the split-fp16 GEMMs, no pass over dZ
-        return _grads_from_dZ(core, R, S, O, h, r, v, Z, needs, core.dtype, dz_bound=g.abs() * (1.0 / B)) + (None,) * 6
+    backward = staticmethod(_stored_loss_backward)
 
 
 def ce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_smoothing=0.0, matrix_free=False,
@@ -1109,9 +1120,7 @@ def score_1vN(core, R, S, O, subject_idx, relation_idx, sigmoid=True, exact=Fals
     ``tables`` (no autograd): the prebuilt relation tables of these parameters (``relation_tables(core, R)``);
     stage 1 then only does the subject-mode contraction -- same bits as without them.
     """
-    needs_grad = torch.is_grad_enabled() and any(
-        isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S, O))
-    if needs_grad:
+    if _wants_grad(core, R, S, O):
         if out_dtype != torch.float32:
             raise RuntimeError("bfloat16 scores are an inference option (no autograd)")
         return _Score1vN.apply(core, R, S, O, subject_idx, relation_idx, sigmoid, exact, sigmoid_mode)
@@ -1590,7 +1599,7 @@ def _candidates(name, t, B, dev):
     K = t.shape[1]
     if K > 1 and t.stride(1) != 1:
         raise RuntimeError(f"{name} must have unit column stride")
-    ld = t.stride(0) if B > 1 else K
+    ld = _ld(t)
     if ld != 0 and ld < K:
         raise RuntimeError(f"{name}: row stride {ld} below K = {K} (rows must not overlap)")
     return t, ld, K
@@ -1648,16 +1657,12 @@ class _ScoreCandidates(torch.autograd.Function):
     def backward(ctx, grad_out):
         core, R, S, O, h, r, cand, v, out = ctx.saved_tensors
         needs = ctx.needs_input_grad
-        pdt = core.dtype                      # bf16 operands: gradients computed in fp32, returned in bf16
         B, K = out.shape
         N, c = O.shape
         dev = out.device
-        g = [None] * 4
         if B == 0 or K == 0:
-            g = [torch.zeros_like(t) if n else None for t, n in zip((core, R, S, O), needs[:4])]
-            return tuple(g) + (None,) * 5
+            return _zero_batch_grads(ctx)
         lib = _lib.load()
-        bf16 = pdt == torch.bfloat16
         grad_out = grad_out.contiguous().float()
         with torch.cuda.device(dev):
             sp = _stream_ptr(dev)
@@ -1672,19 +1677,14 @@ class _ScoreCandidates(torch.autograd.Function):
             gO = torch.empty((N, c), dtype=torch.float32, device=dev) if needs[3] else None
             nws = lib.rtk_score_candidates_bwd_workspace_bytes(B, K, N) if needs[3] else 0
             ws = torch.empty(max(nws, 256), dtype=torch.uint8, device=dev)
-            _lib.check(_entry("rtk_score_candidates_bwd", bf16)(
+            # (the kernel reads O in the operands' own dtype; only the stage-1 backward computes on fp32 copies)
+            _lib.check(_entry("rtk_score_candidates_bwd", O.dtype == torch.bfloat16)(
                 dZ.data_ptr(), K, v.data_ptr(), B, c, O.data_ptr(), N, cand.data_ptr(), ctx.ld, K,
                 dv.data_ptr() if want_dv else None, gO.data_ptr() if needs[3] else None, ws.data_ptr(), ws.numel(), sp),
                 "rtk_score_candidates_bwd")
-        if want_dv:
-            if bf16:
-                core, R, S = core.float(), R.float(), S.float()
-            g[0], g[1], g[2] = _stage1_backward(core, R, S, h, r, dv, needs)
-        g[3] = gO
-        if bf16:
-            g = [x.to(pdt) if x is not None else None for x in g]
+        g = _stage1_backward(*_f32(core, R, S), h, r, dv, needs) if want_dv else (None,) * 3
         # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
-        return tuple(g) + (None,) * 5
+        return _grads_like(g + (gO,), core.dtype) + (None,) * 5
 
 
 def score_candidates(core, R, S, O, subject_idx, relation_idx, candidates, sigmoid=True, sigmoid_mode=None,
@@ -1696,9 +1696,7 @@ def score_candidates(core, R, S, O, subject_idx, relation_idx, candidates, sigmo
     respect to core, R, S and O (bf16 operands: gradients computed in fp32, returned in bf16).  ``tables`` (no
     autograd): prebuilt relation tables, as for ``score_1vN``.  An id outside [0, N) gives a NaN entry and raises
     ``IndexError`` by the ``index_check`` policy."""
-    needs_grad = torch.is_grad_enabled() and any(
-        isinstance(t, torch.Tensor) and t.requires_grad for t in (core, R, S, O))
-    if needs_grad:
+    if _wants_grad(core, R, S, O):
         return _ScoreCandidates.apply(core, R, S, O, subject_idx, relation_idx, candidates, sigmoid, sigmoid_mode)
     op = _Operands(core, R, S, O, subject_idx, relation_idx)
     cand, ld, K = _candidates("candidates", candidates, op.B, op.dev)
@@ -1790,10 +1788,6 @@ def _f32_matrix(name, t, dev=None):
     return t if t.stride(1) == 1 and (t.shape[0] <= 1 or t.stride(0) >= t.shape[1]) else t.contiguous()
 
 
-def _ld(t):
-    return t.stride(0) if t.shape[0] > 1 else t.shape[1]
-
-
 def _pair_rows(core, X, x_idx, w, sp):
     """``rtk_pair_rows_f32`` on the stream ``sp`` -> ``(rows (B, b) fp32, workspace)``."""
     a, b, c = core.shape
@@ -1880,9 +1874,8 @@ class _RelationLogits(torch.autograd.Function):
         pdt = core.dtype                      # bf16 operands: gradients computed in fp32, returned in bf16
         B, dev = u.shape[0], u.device
         if B == 0:
-            return tuple(torch.zeros_like(x) if n else None for x, n in zip((core, R, S, O), needs)) + (None, None)
-        if pdt == torch.bfloat16:
-            core, R, S, O = core.float(), R.float(), S.float(), O.float()
+            return _zero_batch_grads(ctx)
+        core, R, S, O = _f32(core, R, S, O)
         lib = _lib.load()
         a, n_rel = core.shape[0], R.shape[0]
         dZ = grad_out.contiguous().float()
@@ -1904,10 +1897,8 @@ class _RelationLogits(torch.autograd.Function):
             if needs[0]:                      # (ids outside their table were reported by the forward; here they are clamped)
                 g[0] = core_outer(du, S.index_select(0, h.clamp(0, S.shape[0] - 1)),
                                   O.index_select(0, t.clamp(0, O.shape[0] - 1)))
-        if pdt == torch.bfloat16:
-            g = [x.to(pdt) if x is not None else None for x in g]
         # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
-        return tuple(g) + (None, None)
+        return _grads_like(g, pdt) + (None, None)
 
 
 def relation_logits(core, R, S, O, subject_idx, object_idx):
