@@ -560,11 +560,17 @@ int rtk_score_candidates_bf16(const float *v, int64_t batch, int c, const void *
  *   gO[e, :]  = sum_{(d, k): cand[d, k] = e} dZ[d, k] v[d, :]    fp32 (n_ent x c), written in full (rows no
  *               candidate names are 0); v is the fp32 query vector (for _bf16 not rounded: the rule of the 1-vs-N
  *               backward)
- * Either output may be NULL.  Out-of-range candidates add nothing to either.  No float atomics; two runs give the
- * same bits:  dv sums each quarter of a row's list in increasing k and adds the quarters in order;  gO orders the
- * entries d K + k by entity on the device (stable radix sort: counts, offsets, a stable fill), sums each entity's
- * list in increasing d K + k in chunks (batch K / 4096 entries rounded up to 16, clamped to [16, 256]: a function of
- * batch K alone), and adds the chunk sums in chunk order.
+ * Either output may be NULL.  Out-of-range candidates add nothing to either, whatever their dZ (NaN and inf
+ * included).  No float atomics; two runs give the same bits.
+ * dv: a quarter is ceil(K / 4) consecutive k -- quarter i holds the k in [i ceil(K / 4), min(K, (i + 1) ceil(K / 4))),
+ * so trailing quarters may be empty (K = 5: 2, 2, 1, 0 entries).  Per element j each quarter starts from +0 and adds
+ * fmaf(dZ[d, k], O[cand[d, k], j], q_i) in increasing k; then dv[d, j] = ((q0 + q1) + q2) + q3 by fp32 adds, an empty
+ * quarter being +0.  So |dv - exact| <= gamma(ceil(K / 4) + 2) sum_k |dZ||o| per element.  The order depends on K
+ * alone (not on batch, c, ld_dz, ld_cand or n_ent).  dv reads neither v (it must still be non-NULL: the argument rules)
+ * nor the workspace: with gO == NULL, workspace may be NULL and workspace_bytes 0.  K == 0: dv is all +0.
+ * gO orders the entries d K + k by entity on the device (stable radix sort: counts, offsets, a stable fill), sums
+ * each entity's list in increasing d K + k in chunks (batch K / 4096 entries rounded up to 16, clamped to [16, 256]:
+ * a function of batch K alone), and adds the chunk sums in chunk order.
  * The workspace (rtk_score_candidates_bwd_workspace_bytes, 256-byte aligned) is needed when gO is given.
  * Argument rules as the forward, and ld_dz >= K.
  */
