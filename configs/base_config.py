@@ -8,7 +8,10 @@ New fields (not in the reference): ``TrainConfig.scheduler`` -- ``"onecycle"`` i
 hard-codes (OneCycleLR, max_lr 600, ignoring ``learning_rate``), ``"exp"`` is the README's ``lr`` /
 ``lr_decay`` column (``learning_rate`` decayed by ``scheduler_step`` per epoch); ``LogConfig.use_wandb``;
 ``TrainConfig.loss`` -- ``"bce"`` is the reference's ``nn.BCELoss`` on sigmoid scores, ``"ce"`` the softmax
-cross-entropy over the entities (``ops.ce_loss_1vN``).
+cross-entropy over the entities (``ops.ce_loss_1vN``); ``TrainConfig.grad_at`` -- ``"construct"`` differentiates the
+loss at the reference's doubled-rank construct, ``"point"`` at the point's own rank (the same tangent vector,
+``riemannian.TuckerRiemannian.grad``); ``TrainConfig.matrix_free`` -- the loss without the (B, n_ent) score matrix
+(the loss must see an object rank <= 208: with ``grad_at="point"`` that is the manifold rank itself).
 """
 from __future__ import annotations
 
@@ -33,6 +36,8 @@ class TrainConfig(_Dictable):
     scheduler_step: float = 0.995
     scheduler: str = "onecycle"
     loss: str = "bce"                # "ce": softmax cross-entropy over the entities (ops.ce_loss_1vN)
+    grad_at: str = "construct"       # "point": the Riemannian gradient from one backward at the point's own rank
+    matrix_free: bool = False        # the loss without the (B, n_ent) score matrix (object rank seen by the loss <= 208)
 
     base_regularization_coeff: float = 1e-11
     final_regularization_coeff: float = 1e-16

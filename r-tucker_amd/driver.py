@@ -8,7 +8,9 @@ built MI355X-first on this package's pieces:
   term ``BCELoss(score_fn(T), targets)`` of ``train.py:79`` is ``ops.bce_loss_1vN`` (scores, label-smoothed BCE
   and d loss / d logits in HIP kernels; ``targets = (1 - eps) * multi_hot + eps / N`` as ``Dataset.py:51-52``);
 * ``loss_fn(T) = BCE + regularization_coeff * T.norm() ** 2`` is differentiated by the Riemannian optimizer at
-  the doubled-rank construct exactly as the reference's is (``optim.fit(loss_fn, x_k)``, then ``optim.step()``);
+  the doubled-rank construct exactly as the reference's is (``optim.fit(loss_fn, x_k)``, then ``optim.step()``), or,
+  with ``train_cfg.grad_at = "point"``, at the point's own rank (the same tangent vector; ``riemannian.grad``), where
+  ``train_cfg.matrix_free`` trains without the (B, n_ent) score matrix at every rank the reference's README uses;
 * evaluation is ``evaluation.evaluate``: HIP scores + on-device filtered ranking, relation tables cached.
 
 The shuffle uses ``torch.randperm`` on the device with ``drop_last`` semantics (``train.py:227-228``).
@@ -22,6 +24,7 @@ from torch import nn
 
 from . import ops
 from .evaluation import DeviceFilter, evaluate as _evaluate
+from .riemannian import check_grad_at
 from .tucker import SFTucker, Tucker
 from . import tucker as _tucker
 from .utils.storage import Losses, Metrics, StateDict
@@ -41,12 +44,14 @@ def define_optimizer(model, cfg, mode: str, opt: str):
         from .model.asymmetric.optim import RGD, RSGDwithMomentum, RiemannianAdam
         param_list = nn.ParameterList([model.core, model.S.weight, model.R.weight, model.O.weight])
     rank, lr = cfg.model_cfg.manifold_rank, cfg.train_cfg.learning_rate
+    grad_at = getattr(cfg.train_cfg, "grad_at", "construct")
+    check_step_config(grad_at, getattr(cfg.train_cfg, "matrix_free", False), rank)
     if opt == "rsgd":
-        return RSGDwithMomentum(param_list, rank, lr, cfg.train_cfg.momentum_beta)
+        return RSGDwithMomentum(param_list, rank, lr, cfg.train_cfg.momentum_beta, grad_at=grad_at)
     if opt == "rgd":
-        return RGD(param_list, rank, lr)
+        return RGD(param_list, rank, lr, grad_at=grad_at)
     if opt == "adam":
-        return RiemannianAdam(param_list, rank, lr, step_velocity=1)
+        return RiemannianAdam(param_list, rank, lr, step_velocity=1, grad_at=grad_at)
     raise NotImplementedError("Such optimization method is not implemented")
 
 
@@ -74,13 +79,25 @@ class RegularisedLoss:
 LOSSES = ("bce", "ce")          # TrainConfig.loss
 
 
+def check_step_config(grad_at, matrix_free, rank):
+    """Refuse, before any batch, a training step that cannot run: an unknown ``grad_at`` (``riemannian.GRAD_AT``), or
+    the matrix-free loss under ``grad_at="construct"`` at a manifold rank whose DOUBLED object rank is outside the
+    matrix-free kernels' range.  (At the point the kernels see the object rank itself; their own refusals stand.)"""
+    check_grad_at(grad_at, "train_cfg.grad_at")
+    if matrix_free and grad_at == "construct" and 2 * int(rank[2]) > ops._STREAM_MAX_C:
+        raise ValueError(f"train_cfg.matrix_free=true with train_cfg.grad_at=construct: the Riemannian gradient is taken at "
+                         f"the doubled-rank construct, object rank {2 * int(rank[2])} > {ops._STREAM_MAX_C}, outside the "
+                         f"matrix-free range; set train_cfg.grad_at=point (object rank {int(rank[2])})")
+
+
 def batch_loss_fn(model, subject_idx, relation_idx, flt, item_ids, label_smoothing, regularization_coeff,
                   matrix_free=False, loss="bce"):
     """``loss_fn`` of ``train.py:79`` for one batch, as a function of the container ``T``.
     ``regularization_coeff``: a float or a 0-dim device tensor (the captured step keeps it in device memory).
-    ``matrix_free``: ``ops.bce_loss_1vN``'s form without the (B, N) matrix (object rank <= 208: not the Riemannian
-    step's doubled-rank construct).  ``loss``: ``"bce"`` (the reference's) or ``"ce"``, the softmax cross-entropy
-    ``ops.ce_loss_1vN`` over the entities with the same smoothed targets normalised per row."""
+    ``matrix_free``: ``ops.bce_loss_1vN``'s form without the (B, N) matrix, object rank of ``T`` <= 208: under the
+    Riemannian step that is the point's own rank with ``grad_at="point"``, twice that at the doubled-rank construct.
+    ``loss``: ``"bce"`` (the reference's) or ``"ce"``, the softmax cross-entropy ``ops.ce_loss_1vN`` over the entities
+    with the same smoothed targets normalised per row."""
     if loss not in LOSSES:
         raise ValueError(f"batch_loss_fn: unknown loss {loss!r} (one of {', '.join(LOSSES)})")
     data_loss = ops.bce_loss_1vN if loss == "bce" else ops.ce_loss_1vN
@@ -139,21 +156,24 @@ class EagerTrainStep:
 TRAIN_STEP_FACTORY = EagerTrainStep
 
 
-def _captured_step(model, optimizer, train_flt, batch_size, label_smoothing, loss="bce"):
+def _captured_step(model, optimizer, train_flt, batch_size, label_smoothing, loss="bce", matrix_free=False):
     """The per-batch step object, kept on the optimizer so that later epochs reuse it (and its device buffers)."""
     if loss not in LOSSES:
         raise ValueError(f"train_cfg.loss: unknown loss {loss!r} (one of {', '.join(LOSSES)})")
-    key = (id(model), id(train_flt), int(batch_size), float(label_smoothing), TRAIN_STEP_FACTORY, loss)
+    grad_at, matrix_free = getattr(optimizer, "grad_at", "construct"), bool(matrix_free)
+    key = (id(model), id(train_flt), int(batch_size), float(label_smoothing), TRAIN_STEP_FACTORY, loss, grad_at, matrix_free)
     cur = getattr(optimizer, "_rtk_captured", None)
     if cur is None or cur[0] != key:
-        loss_fn = batch_loss_fn if loss == "bce" else functools.partial(batch_loss_fn, loss=loss)
+        check_step_config(grad_at, matrix_free, tuple(model.core.shape))
+        how = ({} if loss == "bce" else {"loss": loss}) | ({"matrix_free": True} if matrix_free else {})
+        loss_fn = functools.partial(batch_loss_fn, **how) if how else batch_loss_fn
         cur = (key, TRAIN_STEP_FACTORY(model, optimizer, train_flt, batch_size, label_smoothing, extract_tensor, loss_fn))
         optimizer._rtk_captured = cur
     return cur[1]
 
 
 def train_one_epoch(model, optimizer, train_flt: DeviceFilter, batch_size, label_smoothing, regularization_coeff=1e-4,
-                    max_batches=None, log=None, loss="bce"):
+                    max_batches=None, log=None, loss="bce", matrix_free=False):
     """``train.py:69-91``: one pass over the (s, r) pairs of the train split; returns the mean loss and mean
     Riemannian gradient norm over the batches.  The batch step (``fit`` + ``step``) runs eagerly (``EagerTrainStep``);
     loss and gradient norm are summed on the device (one synchronisation per epoch instead of the reference's two
@@ -165,7 +185,7 @@ def train_one_epoch(model, optimizer, train_flt: DeviceFilter, batch_size, label
     if max_batches is not None:
         n_batches = min(n_batches, max_batches)
     perm = torch.randperm(n, device=dev)
-    step = _captured_step(model, optimizer, train_flt, batch_size, label_smoothing, loss)
+    step = _captured_step(model, optimizer, train_flt, batch_size, label_smoothing, loss, matrix_free)
     with ops.index_check("deferred"):                   # ids come from the dataset's own vocabulary: one check per epoch
         step.begin_epoch(regularization_coeff)
         for b in range(n_batches):
@@ -206,7 +226,8 @@ def train(model, optimizer, train_set, val_set, test_set, config, regulizer, sch
             train_loss, train_norm = train_one_epoch(model, optimizer, train_flt, tc.train_batch_size, tc.label_smoothig,
                                                      regularization_coeff=regularization_coeff,
                                                      max_batches=max_batches_per_epoch,
-                                                     loss=getattr(tc, "loss", "bce"))
+                                                     loss=getattr(tc, "loss", "bce"),
+                                                     matrix_free=getattr(tc, "matrix_free", False))
         epoch_time = timer.time
         val_metrics, val_loss = evaluate(model, val_set, tc.eval_batch_size, val_flt)
         with timer:

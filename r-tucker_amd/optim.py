@@ -22,7 +22,7 @@ from typing import Callable, Union
 import torch
 from torch.optim import Optimizer
 
-from .riemannian import SFTuckerRiemannian, TuckerRiemannian
+from .riemannian import SFTuckerRiemannian, TuckerRiemannian, check_grad_at
 from .tucker import SFTucker, Tucker
 
 
@@ -61,7 +61,10 @@ def _check_finite(what, vec_or_tensor):
 
 
 class _ManifoldOptimizer(Optimizer):
-    """Shared machinery.  ``symmetric`` selects the manifold and the parameter order.
+    """Shared machinery.  ``symmetric`` selects the manifold and the parameter order; ``grad_at`` the form in which
+    every ``fit`` takes the Riemannian gradient (``"construct"``: the reference's doubled-rank construct; ``"point"``:
+    one backward at the point's own rank, the same tangent vector -- ``TuckerRiemannian.grad``).  Momentum transport
+    (``project``) and the retraction work on the doubled-rank construct either way.
 
     State that survives a step (the previous direction of RSGD, Adam's first moment) is an EXPLICIT rank-2r tensor
     held in persistent buffers: it is built from the tangent vector BEFORE the parameters are overwritten in place
@@ -74,7 +77,8 @@ class _ManifoldOptimizer(Optimizer):
     symmetric = False
     capturable = True          # a step has no host-side state that changes from step to step
 
-    def __init__(self, params, rank, max_lr, **extra):
+    def __init__(self, params, rank, max_lr, grad_at="construct", **extra):
+        self.grad_at = check_grad_at(grad_at, type(self).__name__)
         self.rank = tuple(rank)
         self.max_lr = max_lr
         self.lr = max_lr
@@ -87,6 +91,10 @@ class _ManifoldOptimizer(Optimizer):
     @property
     def geometry(self):
         return SFTuckerRiemannian if self.symmetric else TuckerRiemannian
+
+    def _grad(self, loss_fn, x_k):
+        """``geometry.grad`` in the form this optimizer was built with (``grad_at``: ``riemannian.GRAD_AT``)."""
+        return self.geometry.grad(loss_fn, x_k, at=self.grad_at)
 
     # ---- helpers ---------------------------------------------------------------------------------
     def _normalised(self, rgrad, rgrad_norm, normalize_grad):
@@ -173,7 +181,7 @@ class RGD(_ManifoldOptimizer):
             normalize_grad: Union[float, bool] = 1.):
         """Riemannian gradient of ``loss_fn`` at ``x_k``; returns its Frobenius norm.  ``normalize_grad``:
         ``False`` keeps the gradient's length, a float rescales it to that length."""
-        rgrad, self.loss = self.geometry.grad(loss_fn, x_k)
+        rgrad, self.loss = self._grad(loss_fn, x_k)
         rgrad_norm = rgrad.norm().detach()
         self.direction = self._normalised(rgrad, rgrad_norm, normalize_grad)
         return rgrad_norm
@@ -187,8 +195,8 @@ class RSGDwithMomentum(_ManifoldOptimizer):
     """Riemannian SGD with momentum: the previous direction (kept as an explicit rank-2r tensor) is
     transported to the new point by projection (``asymmetric/optim.py:60-114``, ``symmetric/optim.py:62-107``)."""
 
-    def __init__(self, params, rank, max_lr, momentum_beta=0.9):
-        super().__init__(params, rank, max_lr, momentum_beta=momentum_beta)
+    def __init__(self, params, rank, max_lr, momentum_beta=0.9, grad_at="construct"):
+        super().__init__(params, rank, max_lr, grad_at=grad_at, momentum_beta=momentum_beta)
         self.momentum_beta = momentum_beta
         self.momentum = None
         self._prev = None              # the previous direction as an explicit tensor (persistent buffers)
@@ -200,7 +208,7 @@ class RSGDwithMomentum(_ManifoldOptimizer):
         else:
             self.momentum = geo.TangentVector(x_k, torch.zeros_like(x_k.core))
         _check_finite("momentum projected to the new point", self.momentum)
-        rgrad, self.loss = geo.grad(loss_fn, x_k)
+        rgrad, self.loss = self._grad(loss_fn, x_k)
         _check_finite("loss", self.loss)
         _check_finite("Riemannian gradient", rgrad)
         rgrad_norm = rgrad.norm().detach()
@@ -221,8 +229,8 @@ class RiemannianAdam(_ManifoldOptimizer):
 
     capturable = False         # the bias correction uses a host-side step counter
 
-    def __init__(self, params, rank, max_lr, betas=(0.9, 0.999), eps=1e-8, step_velocity=1):
-        super().__init__(params, rank, max_lr, betas=betas, eps=eps, step_velocity=step_velocity)
+    def __init__(self, params, rank, max_lr, betas=(0.9, 0.999), eps=1e-8, step_velocity=1, grad_at="construct"):
+        super().__init__(params, rank, max_lr, grad_at=grad_at, betas=betas, eps=eps, step_velocity=step_velocity)
         self.betas = betas
         self.eps = eps
         self.step_velocity = step_velocity
@@ -233,7 +241,7 @@ class RiemannianAdam(_ManifoldOptimizer):
 
     def fit(self, loss_fn, x_k, normalize_grad: Union[float, bool] = 1.):
         geo = self.geometry
-        rgrad, self.loss = geo.grad(loss_fn, x_k)
+        rgrad, self.loss = self._grad(loss_fn, x_k)
         rgrad_norm = rgrad.norm().detach()
         b1, b2 = self.betas
         if self._m1 is not None:

@@ -18,7 +18,8 @@ explicit Tucker tensor of rank 2r: factors ``[U_i, dU_i]``, core a 2a x 2b x 2c 
 block (0,0,0) and ``G`` in the three blocks with a single 1.  ``grad`` differentiates
 ``loss_fn(construct(dG, dU))`` at ``(dG, dU) = (G, 0)`` -- which is why the scoring closure is evaluated
 at DOUBLED rank during training -- and maps the partial derivatives to the tangent
-space: ``dU_i <- (I - U_i U_i^T) (d/d dU_i) (G_(i) G_(i)^T)^-1``.
+space: ``dU_i <- (I - U_i U_i^T) (d/d dU_i) (G_(i) G_(i)^T)^-1``.  ``grad(..., at="point")`` takes the same
+partial derivatives from one backward at the point's own rank (``TuckerRiemannian.grad``).
 """
 from __future__ import annotations
 
@@ -115,6 +116,20 @@ def _project_out(U: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
     return M - U @ _tn(U, M)
 
 
+GRAD_AT = ("construct", "point")          # where ``grad`` differentiates ``loss_fn`` (``TrainConfig.grad_at``)
+
+
+def check_grad_at(at: str, who: str = "grad") -> str:
+    if at not in GRAD_AT:
+        raise ValueError(f"{who}: unknown at={at!r} (one of {', '.join(GRAD_AT)})")
+    return at
+
+
+def _leaves(tensors):
+    """Fresh autograd leaves on the storage of (detached) ``tensors``: ``grad(at="point")`` differentiates in them."""
+    return [t.detach().requires_grad_(True) for t in tensors]
+
+
 def _block_core(dG: torch.Tensor, G: torch.Tensor) -> torch.Tensor:
     """The 2a x 2b x 2c core of ``construct``: dG at (0,0,0); G at (1,0,0), (0,1,0), (0,0,1)."""
     a, b, c = G.shape
@@ -169,15 +184,36 @@ class TuckerRiemannian:
     TangentVector = TuckerTangentVector
 
     @staticmethod
-    def grad(loss_fn: Callable[[Tucker], torch.Tensor], x: Tucker, retain_graph: bool = False):
-        """Riemannian gradient of ``loss_fn`` at ``x`` -> ``(TangentVector, loss value)``."""
+    def grad(loss_fn: Callable[[Tucker], torch.Tensor], x: Tucker, retain_graph: bool = False, at: str = "construct"):
+        """Riemannian gradient of ``loss_fn`` at ``x`` -> ``(TangentVector, loss value)``.
+
+        ``at="construct"`` (the reference's form, the default): differentiate ``loss_fn(construct(dG, dU))`` at
+        ``(dG, dU) = (G, 0)``; ``loss_fn`` sees a container of DOUBLED rank.  ``at="point"``: differentiate ``loss_fn``
+        at the point itself, in leaves that stand for its core and its factors; ``loss_fn`` sees a container of the
+        point's own rank.  The construct represents
+
+            dG x (U1,U2,U3) + G x (dU1,U2,U3) + G x (U1,dU2,U3) + G x (U1,U2,dU3),
+
+        so at ``dG = G, dU = 0`` its derivative in ``dG`` is that of ``loss(G x (U1,U2,U3))`` in ``G`` and its derivative
+        in ``dU_i`` is the one in ``U_i`` (for the shared factor of an ``SFTucker``: the derivative in the ONE ``dE`` is
+        the one in ``E``, summed over both of its modes): the two forms give the same tangent vector and the same loss.
+        The one condition: ``loss_fn`` depends on the container only through the tensor it represents (every loss of
+        this package does).  What follows the derivatives -- the analytic regulariser of ``_split_loss``, the gauge
+        projection, the solves with the point's core Gram matrices -- is one tail for both forms.  Any other ``at``
+        raises ``ValueError``."""
+        check_grad_at(at)
         G = x.core.detach()
         Us = [u.detach() for u in x.factors]
-        dG = G.clone().requires_grad_(True)
-        dUs = [torch.zeros_like(u).requires_grad_(True) for u in Us]
         loss_fn, coeff = _split_loss(loss_fn)
+        if at == "point":
+            dG, *dUs = _leaves([G] + Us)
+            T = Tucker(dG, dUs)
+        else:
+            dG = G.clone().requires_grad_(True)
+            dUs = [torch.zeros_like(u).requires_grad_(True) for u in Us]
         with torch.enable_grad():
-            T = Tucker(_block_core(dG, G), [torch.cat([u, d], dim=1) for u, d in zip(Us, dUs)])
+            if at == "construct":
+                T = Tucker(_block_core(dG, G), [torch.cat([u, d], dim=1) for u, d in zip(Us, dUs)])
             loss = loss_fn(T)
             grads = torch.autograd.grad(loss, [dG] + dUs, retain_graph=retain_graph)
         g_core, g_fac = grads[0], grads[1:]
@@ -272,18 +308,27 @@ class SFTuckerRiemannian:
         return sum(_core_gram(G, m, wide=True) for m in range(nreg, nreg + ns))     # only ever inverted
 
     @staticmethod
-    def grad(loss_fn: Callable[[SFTucker], torch.Tensor], x: SFTucker, retain_graph: bool = False):
+    def grad(loss_fn: Callable[[SFTucker], torch.Tensor], x: SFTucker, retain_graph: bool = False,
+             at: str = "construct"):
+        """As ``TuckerRiemannian.grad`` (``at``: the same two forms, the same identity and condition); at the point the
+        leaves are the core, the regular factors and the one shared factor."""
+        check_grad_at(at)
         G = x.core.detach()
         Rs = [u.detach() for u in x.regular_factors]
         E = x.shared_factor.detach()
         nreg, ns = len(Rs), x.num_shared_factors
-        dG = G.clone().requires_grad_(True)
-        dRs = [torch.zeros_like(u).requires_grad_(True) for u in Rs]
-        dE = torch.zeros_like(E).requires_grad_(True)
         loss_fn, coeff = _split_loss(loss_fn)
+        if at == "point":
+            dG, *dRs, dE = _leaves([G] + Rs + [E])
+            T = SFTucker(dG, dRs, ns, dE)
+        else:
+            dG = G.clone().requires_grad_(True)
+            dRs = [torch.zeros_like(u).requires_grad_(True) for u in Rs]
+            dE = torch.zeros_like(E).requires_grad_(True)
         with torch.enable_grad():
-            T = SFTucker(_block_core(dG, G), [torch.cat([u, d], dim=1) for u, d in zip(Rs, dRs)], ns,
-                         torch.cat([E, dE], dim=1))
+            if at == "construct":
+                T = SFTucker(_block_core(dG, G), [torch.cat([u, d], dim=1) for u, d in zip(Rs, dRs)], ns,
+                             torch.cat([E, dE], dim=1))
             loss = loss_fn(T)
             grads = torch.autograd.grad(loss, [dG] + dRs + [dE], retain_graph=retain_graph)
         g_core, g_reg, g_e = grads[0], grads[1:1 + nreg], grads[-1]

@@ -75,6 +75,10 @@ def main():
                     help="what TangentVector.norm() measures (riemannian.EXPERIMENT; DESIGN.md section 8)")
     ap.add_argument("--variant-reg-excluded", action="store_true",
                     help="normalise the step by the DATA term's gradient norm only (riemannian.EXPERIMENT)")
+    ap.add_argument("--grad-at", default="construct", choices=["construct", "point"],
+                    help="where the Riemannian gradient differentiates the loss (train_cfg.grad_at)")
+    ap.add_argument("--matrix-free", action="store_true",
+                    help="the loss without the (B, n_ent) score matrix (train_cfg.matrix_free; needs --grad-at point here)")
     args = ap.parse_args()
     t_start = time.time()
 
@@ -90,6 +94,7 @@ def main():
     k = args.compress
     cfg = wn18rr_readme_config()
     tc = cfg.train_cfg
+    tc.grad_at, tc.matrix_free = args.grad_at, args.matrix_free
     n_epochs = int(math.ceil((args.epochs or tc.num_epoches) / k)) + args.extra_epochs
     reg_steps = max(1, int(round((args.reg_steps or tc.num_regularizer_decreasing_steps) / k)))
     gamma = (args.lr_decay or tc.scheduler_step) ** k
@@ -193,7 +198,7 @@ def main():
             tucker._CHECK = _optim.CHECK_FINITE = (args.debug_from_epoch <= epoch <= (args.debug_to_epoch or 10 ** 9))
         try:
             train_loss, gnorm = driver.train_one_epoch(model, opt, train_flt, tc.train_batch_size, tc.label_smoothig,
-                                                       regularization_coeff=coeff)
+                                                       regularization_coeff=coeff, matrix_free=tc.matrix_free)
         except FloatingPointError as e:
             sv = [torch.linalg.svdvals(model.core.detach().double().movedim(m, 0).reshape(model.core.shape[m], -1)) for m in range(3)]
             log({"event": "first_non_finite_intermediate", "epoch": epoch, "what": str(e),

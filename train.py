@@ -11,7 +11,9 @@ kernels of this package (``--device`` must be a GPU: there is no CPU path); ``--
 DataLoader workers: the split's target lists live on the GPU as a CSR); wandb is optional
 (``LogConfig.use_wandb``); ``--config`` selects a named configuration (``base`` = the reference's shipped
 defaults, ``wn18rr_readme`` / ``fb15k237_readme`` = the recipes of its README); ``--epochs`` / ``--max-batches``
-shorten a run for smoke tests.
+shorten a run for smoke tests; ``--set train_cfg.grad_at=point`` takes the Riemannian gradient from one backward at
+the point's own rank instead of the doubled-rank construct (the same tangent vector), and with it
+``--set train_cfg.matrix_free=true`` trains without the (B, n_ent) score matrix up to object rank 208.
 """
 from __future__ import annotations
 
@@ -44,6 +46,11 @@ def _coerce(target, name, raw, item):
     import typing
     hints = typing.get_type_hints(type(target)) if dataclasses.is_dataclass(target) else {}
     want = hints.get(name)
+    if want is bool:
+        val = {"true": True, "1": True, "yes": True, "false": False, "0": False, "no": False}.get(raw.strip().lower())
+        if val is None:
+            raise SystemExit(f"--set {item}: {name} expects true or false, got {raw!r}")
+        return val
     try:
         if want is float:
             return float(raw)
@@ -92,9 +99,6 @@ def main(argv=None):
     from r_tucker_amd.utils.storage import StateDict
     from r_tucker_amd.utils.utils import set_random_seed
 
-    data = Data(args.data, reverse=True)
-    set_random_seed(args.seed)
-    rt.set_backend("pytorch")
     cfg = NAMED_CONFIGS[args.config]()
     if args.epochs is not None:
         cfg.train_cfg.num_epoches = args.epochs
@@ -112,6 +116,14 @@ def main(argv=None):
     tc = cfg.train_cfg
     if args.checkpoint_path is not None:
         tc.checkpoint_path = args.checkpoint_path
+    try:                                # a step that cannot run is refused here, before the data is read
+        driver.check_step_config(tc.grad_at, tc.matrix_free, cfg.model_cfg.manifold_rank)
+    except ValueError as e:
+        raise SystemExit(str(e))
+
+    data = Data(args.data, reverse=True)
+    set_random_seed(args.seed)
+    rt.set_backend("pytorch")
 
     Model = rt.SymmetricR_TuckER if args.mode == "symmetric" else rt.AsymmetricR_TuckER
     model = Model((len(data.entities), len(data.relations)), cfg.model_cfg.manifold_rank, device=args.device)
