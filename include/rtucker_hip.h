@@ -887,6 +887,46 @@ int rtk_bce_stream_grad_o_part_f32(const void *q_packed, const float *v, int64_t
                                    void *workspace, size_t ws_bytes, void *stream);
 
 /*
+ * The block form on bf16 operands, object rank up to 512 (rtk_bce_stream_bf16.hip): rtk_bce_stream_rows_part_f32 /
+ * rtk_bce_stream_grad_o_part_f32 with O_local in bf16 (n_local x c, no fp32 copy of it is made) and q_packed the bf16
+ * planes of rtk_pack_query_vectors / rtk_query_vectors_bf16; loss_rows_out is float64, dv_out and gO_local_out are
+ * float32.  The whole matrix is the block col0 = 0, n_local = n_ent.  Arithmetic:
+ *   z = sum_k v^_k O_jk with v^ = the planes' bf16 rounding of v, the k-steps summed as rtk_score_packed_bf16 sums them
+ *   (two interleaved chains at c <= 256, one above), so p has that kernel's bits, and those of rtk_score_rank_*_bf16
+ *   and rtk_score_topk_bf16, in both logistic modes; x = p - y with y = (1 - eps) * multi_hot + eps / n_ent, n_ent the
+ *   GLOBAL entity count (entries of other blocks are skipped), 0 where the fp32 p is exactly 1.0f or 0.0f; the logs of
+ *   the BCE terms clamped at -100;
+ *   dv = X O_local (unscaled);  gO_local = X^T (scale[0] * v) with the fp32 v passed to the call, NOT its bf16 rounding.
+ * The second tile product of both sweeps is cut along the output columns: the 32-column tiles are dealt evenly to the
+ * fewest chunks of at most four tiles (128 columns), one grid dimension; every chunk computes the score tile again
+ * (about 1.75 x the MFMAs of an uncut sweep at c = 512, none extra at c <= 128) and one chunk forms the loss partials.
+ * x enters both products as fp16 hi/lo at 2^14; O as ONE fp16 plane at the power of two that brings max |O_local| into
+ * [2^14, 2^15) -- exact for a bf16 value above the fp16 subnormals -- and scale * v as fp16 hi/lo (two and three MFMAs
+ * per k-step).  Accuracy per element against float64 of (v^, O, v): the bounds of rtk_bce_stream_* with the chain error
+ * dz <= 2^-23 * 16 ceil(c / 16) sum_k |v^_k| |O_jk| (derivation and tests: tests/golden/bce_stream_bf16_cases.py,
+ * tests/test_gpu_bce_stream_bf16_kernels.py); partitions at twice those bounds.  Summation orders, determinism (no
+ * float atomics, a static launch sequence, repeated calls give the same bits), max_pos, the error word (bit 3: more
+ * CSR entries than max_pos), flags, batch == 0 and dv_out == NULL as the fp32 forms; dv_out == NULL leaves the bits of
+ * loss_rows_out unchanged.
+ * Covered: c <= 512, c % 8 == 0 and a 16-byte-aligned O_local (the vector row path); anything else gives
+ * RTK_ERR_UNSUPPORTED, the other refusals are the fp32 forms'.
+ * Workspace: rtk_bce_stream_bf16_workspace_bytes(batch, n_local, c, max_pos), valid without a device, 0 for a shape
+ * outside the covered range; the formula of rtk_bce_stream_part_workspace_bytes with cp = 32 * (the padded tile count
+ * chunks * tiles per chunk), n_local does not enter.  rtk_bce_stream_workspace_bytes and
+ * rtk_bce_stream_part_workspace_bytes keep their answers.
+ */
+size_t rtk_bce_stream_bf16_workspace_bytes(int64_t batch, int64_t n_local, int c, int64_t max_pos);
+int rtk_bce_stream_rows_part_bf16(const void *q_packed, int64_t batch, int c, const void *O_local, int64_t n_local,
+                                  int64_t col0, int64_t n_ent, const int64_t *pair_slot, const int64_t *pair_ptr,
+                                  const int64_t *pair_obj, float label_smoothing, unsigned flags,
+                                  double *loss_rows_out, float *dv_out, void *workspace, size_t ws_bytes, void *stream);
+int rtk_bce_stream_grad_o_part_bf16(const void *q_packed, const float *v, int64_t batch, int c, const void *O_local,
+                                    int64_t n_local, int64_t col0, int64_t n_ent, const int64_t *pair_slot,
+                                    const int64_t *pair_ptr, const int64_t *pair_obj, int64_t max_pos,
+                                    float label_smoothing, unsigned flags, const float *scale, float *gO_local_out,
+                                    void *workspace, size_t ws_bytes, void *stream);
+
+/*
  * The 1-vs-all softmax cross-entropy training loss, the other standard loss of 1-vs-all link prediction: what a user
  * of the reference gets by replacing criterion = nn.BCELoss (train.py:76-82, :136) on sigmoid scores with
  * torch.nn.functional.cross_entropy on the logits, the targets of src/data/Dataset.py:43-53 normalised per row.  For

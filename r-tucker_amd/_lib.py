@@ -109,6 +109,10 @@ SIGNATURES = {
     "rtk_bce_stream_rows_part_f32": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, C.c_float, _u, _p, _p, _p, _sz, _p]),
     "rtk_bce_stream_grad_o_part_f32": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _u, _p, _p, _p,
                                              _sz, _p]),
+    "rtk_bce_stream_bf16_workspace_bytes": (_sz, [_i64, _i64, _i, _i64]),
+    "rtk_bce_stream_rows_part_bf16": (_i, [_p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, C.c_float, _u, _p, _p, _p, _sz, _p]),
+    "rtk_bce_stream_grad_o_part_bf16": (_i, [_p, _p, _i64, _i, _p, _i64, _i64, _i64, _p, _p, _p, _i64, C.c_float, _u, _p, _p, _p,
+                                              _sz, _p]),
     "rtk_ce_rows_f32": (_i, [_p, _i64, _i64, _i64, _p, _p, _p, C.c_float, _p, _p, _p]),
     "rtk_ce_grad_f32": (_i, [_p, _i64, _i64, _i64, _p, _p, _p, C.c_float, _p, _p, C.c_float, _p]),
     "rtk_ce_stream_workspace_bytes": (_sz, [_i64, _i64, _i, _i64]),

@@ -31,14 +31,9 @@
 //
 // Both tile products are three f16 MFMAs per k-step on hi/lo halves (x scaled by 2^14; O and s v by a power of two from
 // their largest magnitude), accumulated in fp32.  No float atomics: every sum has a fixed order.
-#include "rtk_stream_kernel.h"
+#include "rtk_bce_link.h"
 
 namespace {
-
-// x of one probability and its BCE term as a negative
-__device__ __forceinline__ float x_of(float p, float t0, bool valid) {
-    return (valid && p != 1.0f && p != 0.0f) ? p - t0 : 0.0f;
-}
 
 // sweep 1's link: the BCE terms of the tile summed per query, x = p - eps / N
 template <int KS, int SG>
@@ -101,29 +96,6 @@ __global__ __launch_bounds__(256) void rows_finish_kernel(int B, int c, int cp, 
     finish_dv_row(d, t, B, c, cp, n_splits, slab, dvpos, o_bound, dv);
 }
 
-// the positives' link: the correction -(1 - eps) (ln p - ln(1 - p)) and dz = -(1 - eps), 0 where p is saturated
-struct BcePos {
-    static __device__ __forceinline__ float coef(float dt, int64_t) { return dt; }
-    template <int SG, int KS>
-    static __device__ __forceinline__ void term(const Frag<float, KS> &f, float acc, float srow, float dt, float &lacc,
-                                                float &dz) {
-        const float p = f.template prob<SG>(acc, srow);
-        lacc += dt * (rtk_clog(p) - rtk_clog(1.0f - p));
-        dz = (p == 1.0f || p == 0.0f) ? 0.f : -dt;
-    }
-};
-
-// sweep 2's link: nothing travels with the query tile
-struct BceGo {
-    static constexpr int QB = 0;
-    float t0;
-    __device__ __forceinline__ void rows4(const unsigned char *, int) {}
-    template <int SG, int KS>
-    __device__ __forceinline__ float x(const Frag<float, KS> &f, float acc, float srow, int, bool valid) const {
-        return x_of(f.template prob<SG>(acc, srow), t0, valid);
-    }
-};
-
 // ---- host side -------------------------------------------------------------------------------------------------
 
 struct BceWs : StreamWs {
@@ -158,7 +130,7 @@ int launch_rows(const unsigned char *qp, int B, int c, const float *O, int N, in
         const int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
         if (rc != RTK_OK) return rc;
     }
-    hipLaunchKernelGGL((pos_kernel<KS, SG, BcePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot, ptr,
+    hipLaunchKernelGGL((pos_kernel<float, KS, SG, BcePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot, ptr,
                        obj, rows_pos, dv ? dvpos : nullptr, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
                        (int32_t *)nullptr, (float *)nullptr);
     constexpr int bytes = RowsLds<KS>::TOTAL;

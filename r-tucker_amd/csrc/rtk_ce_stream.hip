@@ -272,7 +272,7 @@ int launch_fwd(const unsigned char *qp, int B, int c, const float *O, int N, int
     float *part_max = reinterpret_cast<float *>(ws + L.part_max);
     double *part_sum = reinterpret_cast<double *>(ws + L.part_sum), *part_z = reinterpret_cast<double *>(ws + L.part_z);
     double *rows_pos = reinterpret_cast<double *>(ws + L.rows_pos);
-    hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c,
+    hipLaunchKernelGGL((pos_kernel<float, KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c,
                        1.0f - eps, slot, ptr, obj, rows_pos, (float *)nullptr, (const int32_t *)nullptr, (int64_t)0,
                        (int32_t *)nullptr, (int32_t *)nullptr, (float *)nullptr);
     constexpr int bytes = RowsLds<KS>::TOTAL;
@@ -306,7 +306,7 @@ int launch_grad(const unsigned char *qp, const float *v, int B, int c, const flo
     if (dv) {                                                     // sweep 1 with the second tile product
         int rc = rtk_absmax_f32(O, N, c, c, bounds, (void *)st);
         if (rc != RTK_OK) return rc;
-        hipLaunchKernelGGL((pos_kernel<KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt,
+        hipLaunchKernelGGL((pos_kernel<float, KS, CE_SG, CePos>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt,
                            slot, ptr, obj, (double *)nullptr, dvpos, (const int32_t *)nullptr, (int64_t)0, (int32_t *)nullptr,
                            (int32_t *)nullptr, (float *)nullptr);
         constexpr int bytes = RowsLds<KS>::TOTAL;

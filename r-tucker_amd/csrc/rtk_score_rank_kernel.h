@@ -158,7 +158,7 @@ struct Frag<rtk_bf16, KS> {
         return chain_with([&](int, int ks) { return A[ks]; });
     }
     template <int SG>
-    __device__ __forceinline__ float prob(float z, float) const {
+    static __device__ __forceinline__ float prob(float z, float) {
         if (SG == 2) return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(z * -1.4426950408889634f));
         return 1.0f / (1.0f + expf(-z));
     }

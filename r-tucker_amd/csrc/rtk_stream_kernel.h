@@ -1,6 +1,8 @@
-// What the matrix-free training losses share (rtk_bce_stream.hip, rtk_ce_stream.hip; internal header): the two sweeps
-// and the positives' kernel as skeletons that take the loss's link function as a policy, the transposed operand images
-// of the second tile product, the flat lists of the positives and the workspace pieces common to both.
+// What the matrix-free training losses share (rtk_bce_stream.hip, rtk_ce_stream.hip, rtk_bce_stream_bf16.hip; internal
+// header): the two sweeps and the positives' kernel as skeletons that take the loss's link function as a policy, the
+// transposed operand images of the second tile product, the flat lists of the positives and the workspace pieces common
+// to them.  The sweeps here are the fp32 ones; rtk_stream_bf16_kernel.h has those of bf16 entity rows, which share
+// pos_kernel, pack_v_kernel, go_prologue and the workspace layout.
 //
 //   rows_sweep    sweep 1.  The score tile is computed with the QUERY on the lane and the entities in the accumulator
 //                 registers (entity fragments as the A operand, the packed query planes as B), so the 32 x 32 tile of x is
@@ -279,9 +281,11 @@ __global__ __launch_bounds__(256) void pos_fill_kernel(int64_t m, int32_t n_ent,
 //   coef(dt, n)                             the weight of one entry of a list of n (dt = 1 - eps)
 //   term<SG>(f, acc, srow, coef, lacc, dz)  from the accumulated value of the entry (row factor srow, column factor in
 //                                           f): its loss term, added to lacc, and its logit gradient dz
-template <int KS, int SG, typename LK>
+// T: the operand type of O and of the packed planes; the dv share covers 64 lanes x 4 columns (fp32, c <= 208) or
+// x 8 (bf16, c <= 512; the vector row path: c % 8 == 0, O 16-byte aligned).
+template <typename T, int KS, int SG, typename LK>
 __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char *__restrict__ qp, int B,
-                                                            const float *__restrict__ O, int N, int col0, int c, float dt,
+                                                            const T *__restrict__ O, int N, int col0, int c, float dt,
                                                             const int64_t *__restrict__ pair_slot,
                                                             const int64_t *__restrict__ pair_ptr,
                                                             const int64_t *__restrict__ pair_obj,
@@ -289,7 +293,8 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
                                                             const int32_t *__restrict__ off, int64_t max_pos,
                                                             int32_t *__restrict__ ent, int32_t *__restrict__ owner,
                                                             float *__restrict__ dzf) {
-    __shared__ float part[BS_WAVES][256];
+    constexpr int NDV = sizeof(T) == 4 ? 4 : 8;
+    __shared__ float part[BS_WAVES][64 * NDV];
     const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int d = blockIdx.x;
@@ -297,11 +302,13 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
     const int64_t i0 = s >= 0 ? pair_ptr[s] : 0, i1 = s >= 0 ? pair_ptr[s + 1] : 0;
     const float coef = LK::coef(dt, i1 - i0);
     float lacc = 0.f;
-    float dva[4] = {0.f, 0.f, 0.f, 0.f};
+    float dva[NDV];
+#pragma unroll
+    for (int k = 0; k < NDV; ++k) dva[k] = 0.f;
     if (i0 + 32 * wave < i1) {
-        QueryRow<float, KS> q;
+        QueryRow<T, KS> q;
         q.load(qp, d, h);
-        Frag<float, KS> f;
+        Frag<T, KS> f;
         for (int64_t base = i0 + 32 * wave; base < i1; base += 32 * BS_WAVES) {       // wave-uniform
             const int64_t i = base + r;
             const int64_t jr = i < i1 ? pair_obj[i] - col0 : -1;     // local row
@@ -327,10 +334,10 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
                     const float g = __shfl(dz, rr);
                     const int j = __shfl((int)(ok ? jr : 0), rr);
                     if (g != 0.f) {                                // (uniform)
-                        const float *oj = O + (int64_t)j * c;
+                        const T *oj = O + (int64_t)j * c;
 #pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (lane + 64 * k < c) dva[k] = fmaf(g, oj[lane + 64 * k], dva[k]);
+                        for (int k = 0; k < NDV; ++k)
+                            if (lane + 64 * k < c) dva[k] = fmaf(g, rtk_to_f32(oj[lane + 64 * k]), dva[k]);
                     }
                 }
             }
@@ -343,10 +350,11 @@ __global__ __launch_bounds__(64 * BS_WAVES) void pos_kernel(const unsigned char 
     }
     if (dvpos) {
 #pragma unroll
-        for (int k = 0; k < 4; ++k) part[wave][lane + 64 * k] = dva[k];
+        for (int k = 0; k < NDV; ++k) part[wave][lane + 64 * k] = dva[k];
         __syncthreads();
-        const int col = threadIdx.x;
-        if (col < c) dvpos[(int64_t)d * c + col] = ((part[0][col] + part[1][col]) + part[2][col]) + part[3][col];
+#pragma unroll
+        for (int col = threadIdx.x; col < 64 * NDV; col += 64 * BS_WAVES)
+            if (col < c) dvpos[(int64_t)d * c + col] = ((part[0][col] + part[1][col]) + part[2][col]) + part[3][col];
     }
 }
 
@@ -490,9 +498,10 @@ struct StreamWs {
         return p;
     }
 };
-StreamWs stream_layout(int64_t batch, int c, int64_t max_pos) {
+// nct_pad: the column tiles of the slabs and of the images of s v where a sweep pads them (0: nct_of)
+StreamWs stream_layout(int64_t batch, int c, int64_t max_pos, int nct_pad = 0) {
     StreamWs L;
-    const int nct = nct_of((c + 15) / 16);
+    const int nct = nct_pad ? nct_pad : nct_of((c + 15) / 16);
     const size_t B = (size_t)batch, S = (size_t)splits_of(batch), n_mt = (size_t)rtk_cdiv(batch, 32);
     const size_t M = (size_t)(max_pos > 0 ? max_pos : 0);
     L.total = 256;
@@ -525,14 +534,12 @@ int zero_go(const char *fn, float *gO, int64_t rows, int c, hipStream_t st) {
     return gO ? rtk_zero_async(fn, gO, (size_t)rows * c * 4, st) : RTK_OK;
 }
 
-// Sweep 2 with everything before it, for the links LP (positives) and LK (sweep; qx: what travels with its query
-// tiles, LK::QB bytes each): vs = scale v and its packed images, the positives' flat lists (dt = 1 - eps) and the
-// ordered scatter, which writes gO in full, then go_kernel on top of it.  A static launch sequence.
-template <int KS, int SG, typename LP, typename LK>
-int launch_go(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, const int64_t *slot,
-              const int64_t *ptr, const int64_t *obj, int64_t max_pos, float dt, const float *scale, LK lk,
-              const unsigned char *qx, float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
-    constexpr int NCT = nct_of(KS);
+// What comes before sweep 2, for the link LP of the positives: vs = scale v and its packed images of NCT column tiles,
+// the positives' flat lists (dt = 1 - eps) and the ordered scatter, which writes gO in full.
+template <typename T, int KS, int SG, typename LP>
+int go_prologue(const unsigned char *qp, const float *v, int B, int c, int NCT, const T *O, int N, int col0,
+                const int64_t *slot, const int64_t *ptr, const int64_t *obj, int64_t max_pos, float dt, const float *scale,
+                float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
     const int n_mt = (int)rtk_cdiv(B, 32);
     uint32_t *err = reinterpret_cast<uint32_t *>(ws);
     float *bounds = reinterpret_cast<float *>(ws + L.bounds), *vs = reinterpret_cast<float *>(ws + L.vs);
@@ -551,11 +558,22 @@ int launch_go(const unsigned char *qp, const float *v, int B, int c, const float
         hipLaunchKernelGGL(pos_fill_kernel, dim3((unsigned)(rtk_cdiv(max_pos, 256) < 1024 ? rtk_cdiv(max_pos, 256) : 1024)),
                            dim3(256), 0, st, max_pos, (int32_t)N, ent, owner, dzf);
         hipLaunchKernelGGL(pos_offsets_kernel, dim3(1), dim3(256), 0, st, B, slot, ptr, max_pos, off, err);
-        hipLaunchKernelGGL((pos_kernel<KS, SG, LP>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt, slot,
-                           ptr, obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
+        hipLaunchKernelGGL((pos_kernel<T, KS, SG, LP>), dim3((unsigned)B), dim3(64 * BS_WAVES), 0, st, qp, B, O, N, col0, c, dt,
+                           slot, ptr, obj, (double *)nullptr, (float *)nullptr, (const int32_t *)off, max_pos, ent, owner, dzf);
     }
-    rc = rtk_scatter_flat(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
+    return rtk_scatter_flat(fn, ent, owner, dzf, max_pos, N, vs, c, gO, ws + L.sort, st);
+}
+
+// Sweep 2 with everything before it, for the links LP (positives) and LK (sweep; qx: what travels with its query
+// tiles, LK::QB bytes each): go_prologue, then go_kernel on top of the positives' share.  A static launch sequence.
+template <int KS, int SG, typename LP, typename LK>
+int launch_go(const unsigned char *qp, const float *v, int B, int c, const float *O, int N, int col0, const int64_t *slot,
+              const int64_t *ptr, const int64_t *obj, int64_t max_pos, float dt, const float *scale, LK lk,
+              const unsigned char *qx, float *gO, unsigned char *ws, const StreamWs &L, hipStream_t st, const char *fn) {
+    const int rc = go_prologue<float, KS, SG, LP>(qp, v, B, c, nct_of(KS), O, N, col0, slot, ptr, obj, max_pos, dt, scale, gO,
+                                                  ws, L, st, fn);
     if (rc != RTK_OK) return rc;
+    const float *bounds = reinterpret_cast<const float *>(ws + L.bounds);
     // one workgroup per CU: whole entity tiles per slot, no query ranges
     const int n_slots = grid_of(B, N, RTK_N_CU).n_slots;
     return launch_lds<&go_kernel<KS, SG, LK>, GoLds<KS, LK::QB>::TOTAL>(dim3((unsigned)n_slots), dim3(64 * BS_WAVES), st, fn, qp,

@@ -650,7 +650,8 @@ def bce_loss_1vN(core, R, S, O, subject_idx, relation_idx, flt, item_ids, label_
 
     ``matrix_free=True``: the same loss and gradients without the (B, N) matrix (``rtk_bce_stream_*``): nothing that
     grows with B x N is allocated in forward, backward or between them.  float32 operands with ``c <= 208``,
-    ``c % 4 == 0`` (anything else raises; there is no fallback).  ``sigmoid_mode`` ("fast" / "exact", default
+    ``c % 4 == 0`` (anything else raises; there is no fallback; bf16 operands up to ``c = 512`` are served by
+    ``bce_loss_block_1vN`` on the whole range and by ``ShardedEntityScorer.bce_loss_1vN``).  ``sigmoid_mode`` ("fast" / "exact", default
     ``DEFAULT_SIGMOID``) applies to this form only; the probabilities are the ws score kernel's.  ``max_pos``: an upper
     bound on the number of CSR entries of the batch's queries (default ``B * flt.max_list``, which always holds)."""
     if matrix_free:                      # the whole matrix is one block: col0 = 0, n_ent = N, nothing to reduce
@@ -673,7 +674,9 @@ class _HipBlockLoss:
         the name ``who`` of the public function that was called."""
         _require_gpu("core", core)
         if core.dtype != torch.float32:
-            raise RuntimeError(f"{who}: float32 operands only, got {core.dtype} (bf16 operands stay on the matrix form)")
+            served = ("the matrix form, or bce_loss_block_1vN / ShardedEntityScorer.bce_loss_1vN on the whole range"
+                      if who.startswith("bce_loss_1vN") else "the matrix form")
+            raise RuntimeError(f"{who}: float32 operands only, got {core.dtype} (bf16 operands: {served})")
         op = _Operands(core, R, S, O_loc, subject_idx, relation_idx)
         n_local, c = op.O.shape
         if c > _STREAM_MAX_C or c % 4 != 0 or op.O.data_ptr() % 16 != 0:
@@ -735,6 +738,89 @@ class _HipBlockLoss:
     def stage1_backward(core, R, S, h, r, dv, needs):
         """``(g_core, g_R, g_S)`` from the scaled dv."""
         return _stage1_backward(core, R, S, h, r, dv, needs)
+
+
+# Largest object rank of the matrix-free BCE loss on bf16 operands (rtk_bce_stream_*_part_bf16: the second tile product of
+# both sweeps is cut into chunks of 128 output columns).
+_STREAM_MAX_C_BF16 = 512
+# The fp32 rows of gO that sweep 2 writes per call on bf16 operands: the gradient is returned in bf16, so the block's rows
+# go through an fp32 staging buffer of at most this size, a sub-block of rows per call, instead of a whole fp32 gO
+# beside its bf16 copy.
+_GO_STAGE_BYTES = 32 << 20
+
+
+class _HipBlockLossAnyDtype(_HipBlockLoss):
+    """``_HipBlockLoss`` for float32 OR bfloat16 operands: the steps of ``bce_loss_block_1vN`` and
+    ``ShardedEntityScorer.bce_loss_1vN``.  With bf16 operands stage 1 runs on them as given, the sweeps are
+    ``rtk_bce_stream_*_part_bf16`` (no fp32 copy of ``O_loc``), the stage-1 backward runs on fp32 copies of core, R and S
+    (small), and every gradient comes back in bf16, as the matrix form's do (``_grads_like``); the rows of gO go through
+    an fp32 staging buffer of ``_GO_STAGE_BYTES``, a sub-block of rows per call.  The float32 path is the parent's, call
+    for call."""
+
+    @staticmethod
+    def operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who):
+        _require_gpu("core", core)
+        if core.dtype != torch.bfloat16:
+            return _HipBlockLoss.operands(core, R, S, O_loc, subject_idx, relation_idx, col0, n_ent, who)
+        op = _Operands(core, R, S, O_loc, subject_idx, relation_idx)      # one dtype for all four: mixed ones are refused
+        n_local, c = op.O.shape
+        if c > _STREAM_MAX_C_BF16 or c % 8 != 0 or op.O.data_ptr() % 16 != 0:
+            raise RuntimeError(f"{who}: object rank c = {c} outside the matrix-free range of bf16 operands "
+                               f"(c <= {_STREAM_MAX_C_BF16}, c % 8 == 0, 16-byte-aligned O)")
+        if col0 < 0 or n_ent < 1 or col0 + n_local > n_ent:
+            raise RuntimeError(f"{who}: block [{col0}, {col0} + {n_local}) is not a part of [0, n_ent = {n_ent})")
+        return op.core, op.R, op.S, op.O, op.h, op.r
+
+    @staticmethod
+    def rows(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, want_dv):
+        if O_loc.dtype != torch.bfloat16:
+            return _HipBlockLoss.rows(qp, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, eps, sigmoid_mode, want_dv)
+        lib = _lib.load()
+        dev = O_loc.device
+        n_local, c = O_loc.shape
+        flags = _score_flags(True, sigmoid_mode, torch.float32, True)
+        rows = torch.empty(B, dtype=torch.float64, device=dev)
+        dv = torch.empty((B, c), dtype=torch.float32, device=dev) if want_dv else None
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_bce_stream_bf16_workspace_bytes", B, n_local, c, 0))
+            _lib.check(lib.rtk_bce_stream_rows_part_bf16(qp.data_ptr(), B, c, O_loc.data_ptr(), n_local, col0, n_ent,
+                                                         pair_slot.data_ptr(), pair_ptr.data_ptr(), pair_obj.data_ptr(),
+                                                         eps, flags, rows.data_ptr(), dv.data_ptr() if want_dv else None,
+                                                         ws.data_ptr(), ws.numel(), sp), "rtk_bce_stream_rows_part_bf16")
+        return rows, dv
+
+    @staticmethod
+    def grad_o(qp, v, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps, sigmoid_mode, scale):
+        if O_loc.dtype != torch.bfloat16:
+            return _HipBlockLoss.grad_o(qp, v, B, O_loc, col0, n_ent, pair_slot, pair_ptr, pair_obj, max_pos, eps,
+                                        sigmoid_mode, scale)
+        lib = _lib.load()
+        dev = O_loc.device
+        n_local, c = O_loc.shape
+        flags = _score_flags(True, sigmoid_mode, torch.float32, True)
+        gO = torch.empty((n_local, c), dtype=torch.bfloat16, device=dev)
+        # whole 128-row entity tiles per call; a sub-block of a block is a block (rows [col0 + lo, col0 + hi) of n_ent)
+        step = min(n_local, max(128, _GO_STAGE_BYTES // (4 * c) // 128 * 128))
+        stage = torch.empty((step, c), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            sp = _stream_ptr(dev)
+            ws = _workspace(dev, sp, _size("rtk_bce_stream_bf16_workspace_bytes", B, step, c, max_pos))
+            for lo in range(0, n_local, step):
+                n = min(step, n_local - lo)
+                _lib.check(lib.rtk_bce_stream_grad_o_part_bf16(qp.data_ptr(), v.data_ptr(), B, c,
+                                                               O_loc.data_ptr() + 2 * lo * c, n, col0 + lo, n_ent,
+                                                               pair_slot.data_ptr(), pair_ptr.data_ptr(),
+                                                               pair_obj.data_ptr(), max_pos, eps, flags, scale.data_ptr(),
+                                                               stage.data_ptr(), ws.data_ptr(), ws.numel(), sp),
+                           "rtk_bce_stream_grad_o_part_bf16")
+                gO[lo:lo + n].copy_(stage[:n])
+            _strict_check(ws, sp)
+        return gO
+
+    @staticmethod
+    def stage1_backward(core, R, S, h, r, dv, needs):
+        return _grads_like(_stage1_backward(*_f32(core, R, S), h, r, dv, needs), core.dtype)
 
 
 def _block_enter(ctx, steps, core, R, S, O_loc, subject_idx, relation_idx, eps, max_pos, col0, n_ent, all_reduce, who):
@@ -836,11 +922,14 @@ def bce_loss_block_1vN(core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx
     backward, so core / R / S receive their complete gradients, identical on every rank -- do not average them again;
     ``O_loc.grad`` is local.  A block without rows contributes zeros and still calls ``fn``.
 
-    float32, ``c <= 208``, ``c % 4 == 0`` (anything else raises; no fallback); ``sigmoid_mode`` / ``max_pos`` / the
-    ``index_check`` policy as ``bce_loss_1vN(matrix_free=True)``; ``max_pos`` bounds the CSR entries of the batch's
-    queries in all blocks.  Under ``no_grad``, or when core, R and S want no gradient, dv is not computed."""
+    float32 with ``c <= 208``, ``c % 4 == 0``, or bfloat16 (all four operands) with ``c <= 512``, ``c % 8 == 0``
+    (``rtk_bce_stream_*_part_bf16``: the probabilities are the bf16 score kernel's, no fp32 copy of ``O_loc`` is made,
+    the loss is float32 and the gradients come back in bf16 like the matrix form's); anything else raises, there is no
+    fallback.  ``sigmoid_mode`` / ``max_pos`` / the ``index_check`` policy as ``bce_loss_1vN(matrix_free=True)``;
+    ``max_pos`` bounds the CSR entries of the batch's queries in all blocks.  Under ``no_grad``, or when core, R and S
+    want no gradient, dv is not computed."""
     _require_gpu("core", core)
-    return _block_loss(_HipBlockLoss, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids,
+    return _block_loss(_HipBlockLossAnyDtype, core, R, S, O_loc, col0, n_ent, subject_idx, relation_idx, flt, item_ids,
                        label_smoothing, sigmoid_mode, max_pos, all_reduce)
 
 

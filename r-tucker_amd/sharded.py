@@ -393,16 +393,18 @@ class ShardedEntityScorer:
         of O and needs no exchange.  The last shard's zero padding rows are not entities: they add neither loss nor
         smoothing terms and their gradient is 0.  A rank without rows contributes zeros and still takes part in both
         all-reduces.  Without a process group (world size 1) this is ``ops.bce_loss_1vN(..., matrix_free=True)`` bit
-        for bit.
+        for bit.  bfloat16 operands (all four; ``c <= 512``, ``c % 8 == 0``) run the same steps on
+        ``rtk_bce_stream_*_part_bf16`` as in ``ops.bce_loss_block_1vN``, which the call equals bit for bit at world
+        size 1; the gradients come back in bf16 and the all-reduces (B doubles, B x c floats) are unchanged.
 
         Stage 1 and its backward stay replicated: every rank computes all B query vectors from the replicated core,
         R and S (the scorer's ``stage1`` policy does not apply here).
 
-        ``rows_fn`` / ``grad_o_fn`` / ``stage1_bwd_fn`` take the arguments of ``ops._HipBlockLoss.rows`` / ``grad_o``
+        ``rows_fn`` / ``grad_o_fn`` / ``stage1_bwd_fn`` take the arguments of ``ops._HipBlockLossAnyDtype.rows`` / ``grad_o``
         / ``stage1_backward``; tests inject CPU functions (with ``query_vectors_fn`` / ``pack_fn`` for stage 1)."""
         from . import ops
         lo, n_valid = self._real_rows()
-        steps = self._loss_steps(ops._HipBlockLoss, O_loc.dtype, rows=rows_fn, grad_o=grad_o_fn,
+        steps = self._loss_steps(ops._HipBlockLossAnyDtype, O_loc.dtype, rows=rows_fn, grad_o=grad_o_fn,
                                  stage1_backward=stage1_bwd_fn)
         return ops._block_loss(steps, core, R, S, O_loc[:n_valid], lo, self.shards.n_ent, subject_idx, relation_idx, flt,
                                item_ids, label_smoothing, sigmoid_mode, max_pos, self._all_reduce(dist.ReduceOp.SUM))
