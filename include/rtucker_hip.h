@@ -334,6 +334,45 @@ int rtk_query_vectors_bwd_f32(const float *core, int a, int b, int c,
                               const float *dv, float *g_core, float *g_R, float *g_S,
                               void *workspace, size_t workspace_bytes, void *stream);
 
+/*
+ * The same backward without anything of size batch x a*b: neither W[d,i,j] = sum_k G[i,j,k] dv[d,k] nor the Khatri-Rao
+ * operand R[r_d,i] S[h_d,j] is written.  Arguments, the NULL-output rule, refusals and return codes are those of
+ * rtk_query_vectors_bwd_f32; ranks a, b, c up to 1024.  dv and the three outputs are fp32 in both entries.  The _bf16
+ * entry reads core, R and S as bf16 and converts on load (exact; no fp32 copy of an operand is made): its result is the
+ * _f32 entry's on the upcast operands, bit for bit.
+ * Workspace (rtk_query_bwd_stream_workspace_bytes; valid without a device, 0 at batch <= 0), 256-byte aligned pieces:
+ * the gathered fp32 rows R[r_d] (batch x a) and S[h_d] (batch x b), the per-query rows rows_R (batch x a) and rows_S
+ * (batch x b), and the partial sums of rows_R per 128-column tile of b (ceil(b / 128) x batch x a):
+ * 4 batch (2 a + 2 b + ceil(b / 128) a) bytes plus alignment.
+ * THE ORDER OF THE SUMS (deterministic: no float atomics, no split that depends on the batch):
+ *   W[d,i,j]     one fmaf chain over k ascending from zero (fp32 MFMA; k-tiles of 16, the last one zero-padded).  It
+ *                lives in registers only.
+ *   rows_S[d,j]  = sum_i W[d,i,j] R[r_d,i]: one chain fmaf(W, R[r_d,i], acc) over i ascending from zero -- the chain of
+ *                rtk_query_vectors_bwd_f32, so g_S has that entry's values on every input (a zero may differ in sign).
+ *   rows_R[d,i]  = sum_j W[d,i,j] S[h_d,j]: per tile of 128 columns j0 .. j0 + 127 (columns past b count as zeros),
+ *                lane r = 0 .. 31 forms p_r = W[j0+r] S[j0+r], then fmaf(W[j0+r+32], S[j0+r+32], p_r), then the terms of
+ *                + 64 and + 96; the 32 lane sums are combined by a butterfly, p_r += p_(r xor 16), then xor 8, 4, 2, 1;
+ *                the tiles' sums are added in ascending tile order starting from tile 0's.  The bits depend on S[h_d],
+ *                dv[d], the core and the tile width alone, not on the batch size nor on the query's place in the batch.
+ *   g_core       rtk_core_outer_f32 on the gathered rows and dv: one chain over d ascending from zero, no split-K (so
+ *                its bits differ from rtk_query_vectors_bwd_f32's where that entry splits K).
+ *   g_R, g_S     the ordered row scatter of rtk_query_vectors_bwd_f32 on rows_R, rows_S (the same kernel).
+ * Out-of-range ids are clamped, as in rtk_query_vectors_bwd_f32 (the forward has flagged them).
+ */
+size_t rtk_query_bwd_stream_workspace_bytes(int64_t batch, int a, int b, int c);
+int rtk_query_vectors_bwd_stream_f32(const float *core, int a, int b, int c,
+                                     const float *R, int64_t n_rel,
+                                     const float *S, int64_t n_sub,
+                                     const int64_t *rel_idx, const int64_t *sub_idx, int64_t batch,
+                                     const float *dv, float *g_core, float *g_R, float *g_S,
+                                     void *workspace, size_t workspace_bytes, void *stream);
+int rtk_query_vectors_bwd_stream_bf16(const void *core, int a, int b, int c,
+                                      const void *R, int64_t n_rel,
+                                      const void *S, int64_t n_sub,
+                                      const int64_t *rel_idx, const int64_t *sub_idx, int64_t batch,
+                                      const float *dv, float *g_core, float *g_R, float *g_S,
+                                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* Backward of the logistic (R_TuckER.py:48): dZ = dP * P * (1 - P), n contiguous elements. */
 int rtk_sigmoid_grad_f32(const float *dP, const float *P, float *dZ, int64_t n, void *stream);
 

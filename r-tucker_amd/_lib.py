@@ -47,6 +47,9 @@ SIGNATURES = {
     "rtk_absmax_f32": (_i, [_p, _i64, _i64, _i64, _p, _p]),
     "rtk_query_bwd_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
     "rtk_query_vectors_bwd_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "rtk_query_bwd_stream_workspace_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rtk_query_vectors_bwd_stream_f32": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
+    "rtk_query_vectors_bwd_stream_bf16": (_i, [_p, _i, _i, _i, _p, _i64, _p, _i64, _p, _p, _i64, _p, _p, _p, _p, _p, _sz, _p]),
     "rtk_pack_query_vectors": (_i, [_p, _i64, _i, _i, _p, _p]),
     "rtk_relation_tables_bytes": (_sz, [_i64, _i, _i]),
     "rtk_relation_tables_workspace_bytes": (_sz, [_i, _i64, _i, _i, _i]),

@@ -425,7 +425,8 @@ def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, dz_bound=None, scale=None)
     ones: computed in fp32, returned in bf16) and the saved fp32 query vectors, all in HIP kernels with a fixed
     summation order (bit-identical from run to run): dO = dZ^T v and dv = dZ O (split-K slabs added in chunk order) on the split-fp16 MFMA path of the forward
     (``BACKWARD_GEMM = "f32"`` / ``R_TUCKER_AMD_BWD_GEMM=f32``: the exact fp32 MFMA GEMM), then the stage-1
-    backward ``rtk_query_vectors_bwd_f32`` (two more GEMMs and a deterministic row scatter).  ``dz_bound``: a
+    backward ``rtk_query_vectors_bwd_f32`` (two more GEMMs and a deterministic row scatter; above 1 GiB of workspace its
+    stream form, ``stage1_backward_route``).  ``dz_bound``: a
     one-element device tensor >= max|dZ| when the caller knows one (the BCE gradient does); otherwise one
     max-reduction over dZ finds it.  ``scale``: a one-element device tensor s -- the gradients of ``s * dZ`` are
     returned without a pass over dZ: everything is linear in dZ, so s multiplies the small operands
@@ -436,7 +437,8 @@ def _grads_from_dZ(core, R, S, O, h, r, v, dZ, needs, dz_bound=None, scale=None)
     ldz = _ld(dZ)                           # dZ may be the (B, N) view of a padded buffer (bce_loss_1vN)
     a, b, c = core.shape
     pdt = core.dtype
-    core, R, S, Of = (t.contiguous() for t in _f32(core, R, S, O))
+    # (core, R and S go to the stage-1 backward as they are: it makes its fp32 copies only on the route that needs them)
+    Of = (O if pdt == torch.float32 else O.float()).contiguous()
     gO = gcore = gR = gS = None
     sf16 = BACKWARD_GEMM != "f32"
     with torch.cuda.device(dev):
@@ -753,7 +755,8 @@ class _HipBlockLossAnyDtype(_HipBlockLoss):
     """``_HipBlockLoss`` for float32 OR bfloat16 operands: the steps of ``bce_loss_block_1vN`` and
     ``ShardedEntityScorer.bce_loss_1vN``.  With bf16 operands stage 1 runs on them as given, the sweeps are
     ``rtk_bce_stream_*_part_bf16`` (no fp32 copy of ``O_loc``), the stage-1 backward runs on fp32 copies of core, R and S
-    (small), and every gradient comes back in bf16, as the matrix form's do (``_grads_like``); the rows of gO go through
+    (small) on its gemm route and on the bf16 operands themselves on its stream route (``stage1_backward_route``), and
+    every gradient comes back in bf16, as the matrix form's do (``_grads_like``); the rows of gO go through
     an fp32 staging buffer of ``_GO_STAGE_BYTES``, a sub-block of rows per call.  The float32 path is the parent's, call
     for call."""
 
@@ -820,7 +823,7 @@ class _HipBlockLossAnyDtype(_HipBlockLoss):
 
     @staticmethod
     def stage1_backward(core, R, S, h, r, dv, needs):
-        return _grads_like(_stage1_backward(*_f32(core, R, S), h, r, dv, needs), core.dtype)
+        return _grads_like(_stage1_backward(core, R, S, h, r, dv, needs), core.dtype)
 
 
 def _block_enter(ctx, steps, core, R, S, O_loc, subject_idx, relation_idx, eps, max_pos, col0, n_ent, all_reduce, who):
@@ -1711,23 +1714,48 @@ def _candidate_forward(op, cand, ld, K, flags, tables, want_v):
     return out, (v if want_v else None)
 
 
+# The stage-1 backward has two forms.  "gemm" (rtk_query_vectors_bwd_f32) writes W = dv . G^T and the Khatri-Rao operand,
+# two (B, a*b) fp32 matrices, and runs two GEMMs on them; "stream" (rtk_query_vectors_bwd_stream_*) keeps W in registers
+# and needs O(B (a + b)) bytes.  The stream form is taken where the gemm form's workspace exceeds this many bytes.  The
+# limit is a MEMORY policy, not a measured crossover: the two forms have not been timed against each other for it, and
+# below the limit every call is the gemm form's, bit for bit.  (Tests patch it.)
+_STAGE1_BWD_GEMM_BYTES = 1 << 30
+
+
+def stage1_backward_route(B, a, b, c):
+    """``"gemm"`` or ``"stream"``: the form of the stage-1 backward a batch of B queries at rank (a, b, c) takes --
+    ``"stream"`` iff ``rtk_query_bwd_workspace_bytes(B, a, b, c) > _STAGE1_BWD_GEMM_BYTES``."""
+    need = _lib.load().rtk_query_bwd_workspace_bytes(int(B), int(a), int(b), int(c))
+    return "stream" if need > _STAGE1_BWD_GEMM_BYTES else "gemm"
+
+
 def _stage1_backward(core, R, S, h, r, dv, needs):
-    """(g_core, g_R, g_S) fp32 from dv through ``rtk_query_vectors_bwd_f32``."""
+    """(g_core, g_R, g_S) fp32 from the fp32 dv and core, R, S in their own dtype (float32 or bfloat16), by the route of
+    ``stage1_backward_route``.  "gemm": ``rtk_query_vectors_bwd_f32`` on fp32 operands (bf16 ones are upcast first: three
+    small copies).  "stream": ``rtk_query_vectors_bwd_stream_f32`` / ``_bf16`` on the operands as they are -- no copy."""
     lib = _lib.load()
     dev = dv.device
     a, b, c = core.shape
     B = dv.shape[0]
-    gcore = torch.empty_like(core) if needs[0] else None
-    gR = torch.empty_like(R) if needs[1] else None
-    gS = torch.empty_like(S) if needs[2] else None
+    if stage1_backward_route(B, a, b, c) == "gemm":
+        core, R, S = (t.contiguous() for t in _f32(core, R, S))
+        size, fn, name = lib.rtk_query_bwd_workspace_bytes, lib.rtk_query_vectors_bwd_f32, "rtk_query_vectors_bwd_f32"
+    else:
+        core, R, S = core.contiguous(), R.contiguous(), S.contiguous()
+        bf16 = core.dtype == torch.bfloat16
+        size, fn = lib.rtk_query_bwd_stream_workspace_bytes, _entry("rtk_query_vectors_bwd_stream", bf16)
+        name = "rtk_query_vectors_bwd_stream" + ("_bf16" if bf16 else "_f32")
+    gcore = torch.empty(core.shape, dtype=torch.float32, device=dev) if needs[0] else None
+    gR = torch.empty(R.shape, dtype=torch.float32, device=dev) if needs[1] else None
+    gS = torch.empty(S.shape, dtype=torch.float32, device=dev) if needs[2] else None
     with torch.cuda.device(dev):
-        bws = torch.empty(lib.rtk_query_bwd_workspace_bytes(B, a, b, c), dtype=torch.uint8, device=dev)
-        _lib.check(lib.rtk_query_vectors_bwd_f32(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0], S.data_ptr(),
-                                                 S.shape[0], r.data_ptr(), h.data_ptr(), B, dv.data_ptr(),
-                                                 gcore.data_ptr() if needs[0] else None,
-                                                 gR.data_ptr() if needs[1] else None,
-                                                 gS.data_ptr() if needs[2] else None,
-                                                 bws.data_ptr(), bws.numel(), _stream_ptr(dev)), "rtk_query_vectors_bwd_f32")
+        bws = torch.empty(size(B, a, b, c), dtype=torch.uint8, device=dev)
+        _lib.check(fn(core.data_ptr(), a, b, c, R.data_ptr(), R.shape[0], S.data_ptr(), S.shape[0], r.data_ptr(),
+                      h.data_ptr(), B, dv.data_ptr(),
+                      gcore.data_ptr() if needs[0] else None,
+                      gR.data_ptr() if needs[1] else None,
+                      gS.data_ptr() if needs[2] else None,
+                      bws.data_ptr(), bws.numel(), _stream_ptr(dev)), name)
     return gcore, gR, gS
 
 
@@ -1771,7 +1799,7 @@ class _ScoreCandidates(torch.autograd.Function):
                 dZ.data_ptr(), K, v.data_ptr(), B, c, O.data_ptr(), N, cand.data_ptr(), ctx.ld, K,
                 dv.data_ptr() if want_dv else None, gO.data_ptr() if needs[3] else None, ws.data_ptr(), ws.numel(), sp),
                 "rtk_score_candidates_bwd")
-        g = _stage1_backward(*_f32(core, R, S), h, r, dv, needs) if want_dv else (None,) * 3
+        g = _stage1_backward(core, R, S, h, r, dv, needs) if want_dv else (None,) * 3
         # symmetric model: S and O are the same tensor passed twice; autograd sums gS + gO
         return _grads_like(g + (gO,), core.dtype) + (None,) * 5
 
