@@ -1173,6 +1173,30 @@ size_t rtk_scatter_rows_workspace_bytes(int64_t batch);
 int rtk_scatter_rows_f32(const int64_t *idx, const float *rows, int64_t ld_rows, int64_t batch, int n, int64_t n_out,
                          float *out, void *workspace, size_t ws_bytes, void *stream);
 
+/*
+ * The float64 Gram-type product of two tall fp32 blocks (csrc/rtk_tall_gram.hip): what the Cholesky-QR rounds of the
+ * Riemannian step on a row-sharded factor put in front of their all-reduce (smalllinalg.tall_gram_f64_rows).
+ *     C[i, j] = sum_{k < n} A[k, i] * B[k, j]        (p x q) float64, contiguous
+ * A (n x p) and B (n x q) are fp32, row-major at row pitches lda >= p, ldb >= q (the column halves f[:, :k], f[:, k:]
+ * of an n x 2k matrix are operands as they lie).  Every product is formed in float64, where it is exact; every sum is
+ * accumulated in float64 by v_mfma_f64_16x16x4_f64; no float64 copy of an operand is written to memory.  The rows are
+ * cut into a number of equal ranges (the last may be short) that depends on (n, p, q) only; within a range an element
+ * is one chain over the rows in ascending order; the ranges' partial matrices go to the workspace and a second launch
+ * adds them in range order.  No atomics: repeated calls give the same bits.  Always the same two launches, no host
+ * synchronisation (capturable).  Non-finite values propagate.  Rows at or beyond n are never read, nor is anything
+ * beyond column p / q of a row.  16-byte loads are used when both bases and pitches are 16-byte aligned and p % 4 ==
+ * q % 4 == 0, element loads otherwise: the same sums in the same order.  A == B with equal pitch is allowed.
+ * n == 0 writes zeros.
+ * Covered: 1 <= p, q <= 1024 (RTK_ERR_UNSUPPORTED outside), any n >= 0.  Null operands or workspace, n < 0, a pitch
+ * below its column count, a workspace smaller than rtk_tall_gram_f64_workspace_bytes(n, p, q) or not 256-byte aligned:
+ * RTK_ERR_BAD_ARG.  All of these are reported before anything is enqueued; the outputs are untouched.  The size query
+ * is valid without a device, a multiple of 256, 0 for n < 0 or a shape not covered, and at most 64 MiB: it is (number
+ * of ranges) * p * q * 8 bytes and does not grow with n beyond the range count.
+ */
+size_t rtk_tall_gram_f64_workspace_bytes(int64_t n, int p, int q);
+int rtk_tall_gram_f64(const float *A, int64_t lda, const float *B, int64_t ldb, int64_t n, int p, int q, double *C,
+                      void *workspace, size_t ws_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

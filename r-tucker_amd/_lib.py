@@ -133,6 +133,8 @@ SIGNATURES = {
     "rtk_core_outer_f32": (_i, [_p, _i64, _i, _p, _i64, _i, _p, _i64, _i, _i64, _p, _p]),
     "rtk_scatter_rows_workspace_bytes": (_sz, [_i64]),
     "rtk_scatter_rows_f32": (_i, [_p, _p, _i64, _i64, _i, _i64, _p, _p, _sz, _p]),
+    "rtk_tall_gram_f64_workspace_bytes": (_sz, [_i64, _i, _i]),
+    "rtk_tall_gram_f64": (_i, [_p, _i64, _p, _i64, _i64, _i, _i, _p, _p, _sz, _p]),
 }
 
 _lib = None

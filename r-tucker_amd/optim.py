@@ -138,7 +138,7 @@ class _ManifoldOptimizer(Optimizer):
                 cur = SFTucker(built.core.clone(), [f.clone() for f in built.regular_factors], built.num_shared_factors,
                                built.shared_factor.clone())
             else:
-                cur = Tucker(built.core.clone(), [f.clone() for f in built.factors])
+                cur = Tucker(built.core.clone(), [f.clone() for f in built.factors], row_sum=built.row_sum)
             setattr(self, slot, cur)
         else:
             for dst, src in zip(self._tensors_of(cur), self._tensors_of(built)):

@@ -28,7 +28,7 @@ from typing import Callable, List, Optional, Sequence
 import torch
 
 from .smalllinalg import spd_inverse, spd_inverse_many, wide_gram
-from .tucker import SFTucker, Tucker, _mode_dot, _tn, _unfold
+from .tucker import SFTucker, Tucker, _mode_dot, _summed, _tn, _unfold
 
 
 def _core_gram(core: torch.Tensor, mode: int, wide: bool = False) -> torch.Tensor:
@@ -111,9 +111,9 @@ def _solve_right_many(mats, grams):
     return [m @ inv.to(m.dtype) for m, inv in zip(mats, invs)]
 
 
-def _project_out(U: torch.Tensor, M: torch.Tensor) -> torch.Tensor:
-    """(I - U U^T) M"""
-    return M - U @ _tn(U, M)
+def _project_out(U: torch.Tensor, M: torch.Tensor, row_sum=None) -> torch.Tensor:
+    """(I - U U^T) M  (``row_sum``: U and M are this rank's rows of row-sharded matrices, ``Tucker.row_sum``)"""
+    return M - U @ _tn(U, M, row_sum)
 
 
 GRAD_AT = ("construct", "point")          # where ``grad`` differentiates ``loss_fn`` (``TrainConfig.grad_at``)
@@ -167,17 +167,18 @@ class TuckerTangentVector:
         G = self.point.core
         s = (self.delta_core * self.delta_core).sum()
         for i, d in enumerate(self.delta_factors):
+            rs = self.point._rs(i)
             if EXPERIMENT["norm"] == "coordinate":
-                s = s + (d * d).sum()
+                s = s + _summed((d * d).sum(), rs)
             else:
-                s = s + (_tn(d, d) * _core_gram(G, i)).sum()
+                s = s + (_tn(d, d, rs) * _core_gram(G, i)).sum()
         return torch.sqrt(torch.clamp(s, min=0.0))
 
     def construct(self) -> Tucker:
         x = self.point
         return Tucker(_block_core(self.delta_core, x.core),
                       [torch.cat([u, d], dim=1) for u, d in zip(x.factors, self.delta_factors)],
-                      orth_cols=[u.shape[1] for u in x.factors])
+                      orth_cols=[u.shape[1] for u in x.factors], row_sum=x.row_sum)
 
 
 class TuckerRiemannian:
@@ -207,13 +208,13 @@ class TuckerRiemannian:
         loss_fn, coeff = _split_loss(loss_fn)
         if at == "point":
             dG, *dUs = _leaves([G] + Us)
-            T = Tucker(dG, dUs)
+            T = Tucker(dG, dUs, row_sum=x.row_sum)
         else:
             dG = G.clone().requires_grad_(True)
             dUs = [torch.zeros_like(u).requires_grad_(True) for u in Us]
         with torch.enable_grad():
             if at == "construct":
-                T = Tucker(_block_core(dG, G), [torch.cat([u, d], dim=1) for u, d in zip(Us, dUs)])
+                T = Tucker(_block_core(dG, G), [torch.cat([u, d], dim=1) for u, d in zip(Us, dUs)], row_sum=x.row_sum)
             loss = loss_fn(T)
             grads = torch.autograd.grad(loss, [dG] + dUs, retain_graph=retain_graph)
         g_core, g_fac = grads[0], grads[1:]
@@ -222,8 +223,8 @@ class TuckerRiemannian:
             g_core = g_core + (2.0 * coeff) * G
             loss = loss + coeff * (G * G).sum()
         grams = _point_grams(x, range(len(Us)))
-        deltas = _solve_right_many([_project_out(u, g) for u, g in zip(Us, g_fac)], grams)
-        pt = x if x.core is G else Tucker(G, Us)
+        deltas = _solve_right_many([_project_out(u, g, x._rs(i)) for i, (u, g) in enumerate(zip(Us, g_fac))], grams)
+        pt = x if x.core is G else Tucker(G, Us, row_sum=x.row_sum)
         tv = TuckerTangentVector(pt, g_core, deltas)
         if coeff is not None and not EXPERIMENT["reg_in_norm"]:
             tv._norm_override = TuckerTangentVector(pt, g_core_data, deltas).norm().detach()
@@ -234,7 +235,7 @@ class TuckerRiemannian:
         """Orthogonal projection of an explicit Tucker tensor ``Z`` onto the tangent space at ``x``."""
         G = x.core
         Us = x.factors
-        Ms = [_tn(u, v) for u, v in zip(Us, Z.factors)]          # r_i x k_i
+        Ms = [_tn(u, v, x._rs(i)) for i, (u, v) in enumerate(zip(Us, Z.factors))]          # r_i x k_i
         dG = Z.core
         for i, m in enumerate(Ms):
             dG = _mode_dot(dG, m, i)
@@ -245,7 +246,7 @@ class TuckerRiemannian:
                 if j != i:
                     t = _mode_dot(t, m, j)
             w = v @ (_unfold(t, i) @ _unfold(G, i).transpose(0, 1))           # n_i x r_i
-            ws.append(_project_out(u, w))
+            ws.append(_project_out(u, w, x._rs(i)))
         deltas = _solve_right_many(ws, _point_grams(x, range(len(Us))))
         return TuckerTangentVector(x, dG, deltas)
 

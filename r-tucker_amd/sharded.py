@@ -21,6 +21,10 @@ import torch
 import torch.distributed as dist
 
 
+def _identity(t):
+    return t
+
+
 class EntityShards:
     """Row partition of ``n_ent`` entities over ``world`` ranks."""
 
@@ -161,6 +165,27 @@ class ShardedEntityScorer:
         if self.world == 1:
             return None
         return lambda t: dist.all_reduce(t, op=op, group=self.group)
+
+    @property
+    def row_sum(self):
+        """``fn(t) -> t``: the SUM all-reduce of a small tensor in place over this scorer's group (the identity at world
+        size 1) -- the entry of ``Tucker.row_sum`` for a factor whose rows are sharded as ``local_block`` shards them."""
+        if self.world == 1:
+            return _identity
+
+        def fn(t):
+            c = t if t.is_contiguous() else t.contiguous()
+            dist.all_reduce(c, op=dist.ReduceOp.SUM, group=self.group)
+            return t if c is t else t.copy_(c)
+        return fn
+
+    def tucker(self, core, R, S, O_loc):
+        """The point ``core x (R, S, O)`` of the asymmetric model with O row-sharded: a ``Tucker`` on this rank's block
+        ``O_loc`` whose Riemannian operations (gradient, projection, norms, retraction: ``riemannian.py``, ``optim.py``)
+        complete every sum over O's rows with one small all-reduce.  Core, R and S are replicated and come out of a step
+        identical on every rank; the padding rows of the last shard stay zero."""
+        from .tucker import Tucker
+        return Tucker(core, [R, S, O_loc], row_sum=[None, None, self.row_sum])
 
     def _loss_steps(self, default, dtype, **injected):
         """The steps of a block loss: the class ``default`` of ``ops``, or, when a test injects CPU functions (the

@@ -182,6 +182,37 @@ def tall_gram_f64(D: torch.Tensor) -> torch.Tensor:
     return torch.bmm(Dc.transpose(1, 2), Dc).sum(0)
 
 
+def tall_gram_f64_rows(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
+    """``A^T B`` (p x q, float64) of two tall blocks with the same rows, every product and sum in float64, WITHOUT a
+    float64 copy of the operands: what a rank contributes to the Gram matrix of a row-sharded block (the caller sums
+    the results over the ranks, ``Tucker.row_sum``).  fp32 GPU operands go through ``rtk_tall_gram_f64``
+    (csrc/rtk_tall_gram.hip: the rows are read as they lie, through their pitch -- column slices of one matrix are
+    operands without a copy; p, q <= 1024, wider raises); anything else (the float64 CPU tensors of the tests) through
+    a float64 torch product.  Not differentiable."""
+    A, B = A.detach(), B.detach()
+    if not (A.is_cuda and A.dtype == torch.float32 and B.dtype == torch.float32):
+        return A.double().transpose(0, 1) @ B.double()
+    from . import _lib
+    lib = _lib.load()
+    n, p = A.shape
+    q = B.shape[1]
+    if B.shape[0] != n or B.device != A.device:
+        raise ValueError("tall_gram_f64_rows: A and B must hold the same rows on one device")
+    if n == 0:
+        return torch.zeros((p, q), dtype=torch.float64, device=A.device)
+    A = A if (A.stride(1) == 1 or p == 1) and (A.stride(0) >= p or n == 1) else A.contiguous()
+    B = B if (B.stride(1) == 1 or q == 1) and (B.stride(0) >= q or n == 1) else B.contiguous()
+    lda = A.stride(0) if n > 1 else p
+    ldb = B.stride(0) if n > 1 else q
+    need = lib.rtk_tall_gram_f64_workspace_bytes(n, p, q)
+    ws = torch.empty(max(need, 256), dtype=torch.uint8, device=A.device)
+    C = torch.empty((p, q), dtype=torch.float64, device=A.device)
+    with torch.cuda.device(A.device):
+        _lib.check(lib.rtk_tall_gram_f64(A.data_ptr(), lda, B.data_ptr(), ldb, n, p, q, C.data_ptr(), ws.data_ptr(),
+                                         ws.numel(), torch.cuda.current_stream(A.device).cuda_stream), "rtk_tall_gram_f64")
+    return C
+
+
 def _wide_to_square(M: torch.Tensor) -> torch.Tensor:
     """A p x p matrix with the left singular vectors and singular values of a very wide ``M (p x m)``, m >> p: the
     transposed Cholesky factor of ``M M^T`` accumulated in float64 (the relation-mode unfolding of the WN18RR

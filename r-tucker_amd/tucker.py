@@ -30,10 +30,44 @@ from . import smalllinalg as _sl
 from .smalllinalg import dominant_left_subspace, gram_factor, gram_factor_many
 
 
-def _tn(A: torch.Tensor, B: torch.Tensor) -> torch.Tensor:
-    """``A.T @ B`` -- the Gram-type product (tall-skinny on the GPU: split-K HIP GEMM, ``ops.gram_tn``)."""
+class _RowSum(torch.autograd.Function):
+    """``fn`` (a SUM over the ranks, in place) on a copy of ``t``.  Every rank holds one term of the complete tensor and
+    goes on with the same loss, so the gradient of the complete tensor is each term's gradient: backward is the
+    identity."""
+
+    @staticmethod
+    def forward(ctx, t, fn):
+        return fn(t.detach().clone())
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def _summed(t: torch.Tensor, row_sum) -> torch.Tensor:
+    """``t``, a product that summed over the rows of a factor, completed over the ranks that share those rows:
+    ``row_sum`` is the factor's entry of ``Tucker.row_sum`` (None: the factor is whole here, ``t`` is returned as it
+    is).  ``t`` is a fresh tensor and is summed in place, through ``_RowSum`` where autograd follows it."""
+    if row_sum is None:
+        return t
+    if t.requires_grad:
+        return _RowSum.apply(t, row_sum)
+    return row_sum(t)
+
+
+def _tn(A: torch.Tensor, B: torch.Tensor, row_sum=None) -> torch.Tensor:
+    """``A.T @ B`` -- the Gram-type product (tall-skinny on the GPU: split-K HIP GEMM, ``ops.gram_tn``); with
+    ``row_sum``, of row-sharded ``A`` and ``B``: this rank's rows, then the sum over the ranks (``_summed``)."""
     from .ops import gram_tn
-    return gram_tn(A, B)
+    return _summed(gram_tn(A, B), row_sum)
+
+
+def _gram64(D: torch.Tensor, row_sum=None) -> torch.Tensor:
+    """``D^T D`` in float64: ``smalllinalg.tall_gram_f64`` of a whole block; of a row-sharded one this rank's rows
+    (``smalllinalg.tall_gram_f64_rows``: the HIP kernel on fp32 GPU rows) and the sum over the ranks."""
+    if row_sum is None:
+        return _sl.tall_gram_f64(D)
+    return row_sum(_sl.tall_gram_f64_rows(D, D))
 
 
 def _mode_dot(core: torch.Tensor, mat: torch.Tensor, mode: int) -> torch.Tensor:
@@ -93,17 +127,19 @@ def _dbg(what: str, t: torch.Tensor) -> None:
                                  f"first at {bad[0].tolist()}; finite abs max {t[torch.isfinite(t)].abs().max().item() if bad.shape[0] < t.numel() else 'n/a'}")
 
 
-def _orth_tall_many(Ds):
+def _orth_tall_many(Ds, row_sums=None):
     """``[(Q, R), ...]`` with ``D = Q R``, Q orthonormal columns, R (k x k, float64) upper triangular, for tall-skinny
     blocks by two rounds of Cholesky QR: the Gram matrices are accumulated in float64 (a batched product over row
     chunks), the k x k factors and their inverses come from ``smalllinalg.gram_factor_many`` (float64, equilibrated,
     shifted: no failure path, no host synchronisation; blocks of one width share a launch).  rocSOLVER's Householder
     ``geqrf`` spends 90 ms on a 40 943 x 400 factor; this is four chip-filling GEMMs per block.  A column of zeros
-    stays zero (its row of R is zero)."""
+    stays zero (its row of R is zero).  ``row_sums[i]``: block i is this rank's rows of a row-sharded block (both Gram
+    matrices are completed over the ranks; ``Q`` is this rank's rows, ``R`` the same on every rank)."""
     f32 = Ds[0].dtype == torch.float32
+    row_sums = [None] * len(Ds) if row_sums is None else row_sums
     # (float64 accumulation: the block may be rank deficient to fp32 precision, and its Gram matrix must stay positive
     # semi-definite to well below the shift -- smalllinalg.tall_gram_f64)
-    S1 = [_sl.tall_gram_f64(D) for D in Ds]
+    S1 = [_gram64(D, rs) for D, rs in zip(Ds, row_sums)]
     for S in S1:
         _dbg("Gram matrix of the new factor block", S)
     XR1 = gram_factor_many(S1, shift=3e-6 if f32 else None)          # fp32 block: |X| <= 600 / column norm, Q = D X in fp32
@@ -117,7 +153,7 @@ def _orth_tall_many(Ds):
                 f"{S.diagonal().min().item():.3e} max {S.diagonal().max().item():.3e}; |X| max {X1.abs().max().item():.3e} at "
                 f"{divmod(int(X1.abs().argmax()), X1.shape[1])}; diag X last four {X1.diagonal()[-4:].tolist()}; "
                 f"non-finite in D {int((~torch.isfinite(D)).sum())}, in S {int((~torch.isfinite(S)).sum())}, in X {int((~torch.isfinite(X1)).sum())}")
-    XR2 = gram_factor_many([_sl.tall_gram_f64(Q) for Q in Qs], shift=1e-6 if f32 else None)
+    XR2 = gram_factor_many([_gram64(Q, rs) for Q, rs in zip(Qs, row_sums)], shift=1e-6 if f32 else None)
     return [(Q @ X2.to(Q.dtype), R2 @ R1) for Q, (_, R1), (X2, R2) in zip(Qs, XR1, XR2)]
 
 
@@ -125,11 +161,12 @@ def _orth_tall(D: torch.Tensor):
     return _orth_tall_many([D])[0]
 
 
-def _round_tangent_step(core: torch.Tensor, pairs, mode_factor, ranks):
+def _round_tangent_step(core: torch.Tensor, pairs, mode_factor, ranks, row_sum=None):
     """Truncated HOSVD of ``core x_m [U_f(m), D_f(m)]`` where every ``U`` has orthonormal columns and
     ``U^T D = 0`` up to rounding -- the shape ``TangentVector.construct()`` produces (``pairs[f] = (U, D)``,
     ``mode_factor[m]`` = which pair serves core axis m: (0,1,2) for Tucker, (0,1,1) for the shared-factor tensor;
-    ``ranks[f]`` the target rank of that factor).  Returns ``(new core, [new factor per pair])``.
+    ``ranks[f]`` the target rank of that factor; ``row_sum[f]``: pair f holds this rank's rows of a row-sharded factor,
+    ``Tucker.row_sum``).  Returns ``(new core, [new factor per pair])``.
 
     1. ``D = Q R_d`` (thin QR of the NEW block only, Cholesky QR), so ``[U, D] = [U, Q] [[I, 0], [0, R_d]]`` (the gauge
        condition makes ``[U, Q]`` orthonormal; what rounding leaves of ``U^T D`` is removed by step 4);
@@ -141,8 +178,9 @@ def _round_tangent_step(core: torch.Tensor, pairs, mode_factor, ranks):
     4. the new factor ``[U, Q] W`` is re-orthonormalised by one more Cholesky QR round so drift cannot add up
        over the steps, its triangular factor absorbed into the core."""
     dt = core.dtype
+    row_sum = [None] * len(pairs) if row_sum is None else list(row_sum)
     blocks, bases = [], []
-    for (U, D), (Q, Rd) in zip(pairs, _orth_tall_many([D for _, D in pairs])):   # U^T D = 0 (gauge): [U, Q] is orthonormal
+    for (U, D), (Q, Rd) in zip(pairs, _orth_tall_many([D for _, D in pairs], row_sum)):   # U^T D = 0 (gauge): [U, Q] is orthonormal
         r = U.shape[1]
         k = r + D.shape[1]
         blk = torch.zeros((k, k), dtype=torch.float64, device=core.device)
@@ -185,7 +223,7 @@ def _round_tangent_step(core: torch.Tensor, pairs, mode_factor, ranks):
             r = U.shape[1]
             Wd = W.to(dt)
             news.append(U @ Wd[:r] + Q @ Wd[r:])
-        Ss = [_tn(nu, nu) for nu in news]
+        Ss = [_tn(nu, nu, row_sum[f]) for f, nu in zip(g, news)]
         for S in Ss:
             _note_health((S - torch.eye(S.shape[0], dtype=S.dtype, device=S.device)).abs().max())
         for f, W, nu, (X, Rfix) in zip(g, Ws, news, gram_factor_many(Ss, shift=0.0 if dt == torch.float64 else 1e-7)):
@@ -212,9 +250,17 @@ class Tucker:
     """``X = core x_0 factors[0] x_1 factors[1] x_2 factors[2]`` with factors
     ``[R (nR,a), S (N,b), O (N,c)]`` and core axes (relation, subject, object)."""
 
-    def __init__(self, core: torch.Tensor, factors: Sequence[torch.Tensor], orth_cols: Sequence[int] = None):
+    def __init__(self, core: torch.Tensor, factors: Sequence[torch.Tensor], orth_cols: Sequence[int] = None,
+                 row_sum: Sequence = None):
         self.core = core
         self.factors = list(factors)
+        # row_sum[i] is None when factor i is whole in this process; otherwise ``factors[i]`` holds this rank's rows of a
+        # row-sharded factor and row_sum[i] is a callable ``fn(t) -> t`` that sums a small tensor in place over the ranks
+        # sharing it and returns it (``ShardedEntityScorer.row_sum``).  Every product that sums over the rows of such a
+        # factor is completed with it; everything else on the factor is row-local.
+        self.row_sum = list(row_sum) if row_sum is not None and any(fn is not None for fn in row_sum) else None
+        if self.row_sum is not None and len(self.row_sum) != len(self.factors):
+            raise ValueError("row_sum needs one entry (None or a callable) per factor")
         # optional hint for round(): factor i starts with orth_cols[i] orthonormal columns that are orthogonal
         # to its remaining ones (set by TangentVector.construct(); never required)
         self.orth_cols = list(orth_cols) if orth_cols is not None else None
@@ -227,8 +273,12 @@ class Tucker:
     def shape(self):
         return tuple(f.shape[0] for f in self.factors)
 
+    def _rs(self, i: int):
+        """Factor i's row sum (None: the factor is whole here)."""
+        return None if self.row_sum is None else self.row_sum[i]
+
     def norm(self) -> torch.Tensor:
-        return _gram_norm(self.core, [_tn(f, f) for f in self.factors])
+        return _gram_norm(self.core, [_tn(f, f, self._rs(i)) for i, f in enumerate(self.factors)])
 
     def full(self) -> torch.Tensor:
         t = self.core
@@ -241,8 +291,12 @@ class Tucker:
         ``TangentVector.construct()`` (``orth_cols`` set) takes the structured, synchronisation-free path."""
         if self.orth_cols is not None:
             pairs = [(f[:, :k], f[:, k:]) for f, k in zip(self.factors, self.orth_cols)]
-            core, new = _round_tangent_step(self.core, pairs, list(range(len(pairs))), [int(r) for r in rank])
-            return Tucker(core, new)
+            core, new = _round_tangent_step(self.core, pairs, list(range(len(pairs))), [int(r) for r in rank],
+                                            row_sum=self.row_sum)
+            return Tucker(core, new, row_sum=self.row_sum)
+        if self.row_sum is not None:
+            raise NotImplementedError("Tucker.round: a row-sharded factor is rounded on the structured path only "
+                                      "(a tensor from TangentVector.construct())")
         core = self.core
         qs = []
         for i, f in enumerate(self.factors):
@@ -263,10 +317,10 @@ class Tucker:
         core = self.core.new_zeros((a0 + a1, b0 + b1, c0 + c1))
         core[:a0, :b0, :c0] = self.core
         core[a0:, b0:, c0:] = other.core
-        return Tucker(core, [torch.cat([f, g], dim=1) for f, g in zip(self.factors, other.factors)])
+        return Tucker(core, [torch.cat([f, g], dim=1) for f, g in zip(self.factors, other.factors)], row_sum=self.row_sum)
 
     def __rmul__(self, scalar) -> "Tucker":
-        return Tucker(scalar * self.core, list(self.factors))
+        return Tucker(scalar * self.core, list(self.factors), row_sum=self.row_sum)
 
 
 class SFTucker:
